@@ -1,6 +1,6 @@
 """Headline benchmark: up-scaled frames/s of the GAN train step at 256->512 (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -17,7 +17,16 @@ Secondary lines (same JSON format):
     --dtype bf16              C3/C4's arithmetic: bf16 activations in G and D, fp32 accumulation / statistics / master weights
     --config c5               BASELINE.json configs[4]: inference-only generator, batch 32, bf16, one hipGraph replay per batch
 
-Prints ONE JSON line (rank 0).  Extra objects:
+A plain run sets up, warms up (W steps), times K steps and prints ONE JSON line (rank 0): `value` frames/s, `ms_per_step` the
+wall time of one timed step.  Everything else is behind --full.
+
+    --dump-outputs DIR        after the timed steps, what the last timed step handed its caller, as DIR/<name>.npy (float32 /
+                              float64, at most DUMP_BYTES in all; a larger array is a fixed, seeded sample of its elements).
+                              Train step: the four losses and the trained G and D (flat parameter and state buffers); C5: the
+                              up-scaled frames.  Inputs and initial weights are seeded: the same arguments give the same inputs.
+    --full                    also the extra objects below (their own eager passes after the timed region and a CPU run)
+
+Extra objects (--full only):
   roofline     -- the dominant kernel: algorithmic FLOPs (or bytes) per launch / mean launch duration measured with HIP
                   events on the launch stream, against the peak that bounds it; `traffic` = measured HBM bytes per launch
                   looked up BY KERNEL NAME AND SHAPE in profiles/pmc_traffic.json (written by scripts/pmc_to_json.py from
@@ -41,6 +50,25 @@ PEAK_F32_MFMA_TFLOPS = 157.3        # /opt/skills/guides/MI355X_MICROARCH.md, "P
 PEAK_BF16_MFMA_TFLOPS = 2500.0      # same guide: ~2.5 PF dense
 PEAK_HBM_GBS = 8000.0               # same guide: HBM3E 8.0 TB/s spec
 METRIC = "upscaled frames/s (train step, G+D fwd+bwd) at 256->512"
+DUMP_BYTES = 60 * 10 ** 6           # --dump-outputs: total payload of the .npy files
+
+
+def dump_outputs(path, arrays):
+    """arrays: {name: numpy array} -> path/<name>.npy in float32 (float64 kept), DUMP_BYTES at most in all.  Smallest first, an
+    array that fits its fair share of what is left is written whole; a larger one becomes a sample of its flattened elements at
+    indices drawn with a fixed seed (the same indices for the same sizes, every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v if v.dtype in (np.float32, np.float64) else v.astype(np.float32)) for k, v in arrays.items()}
+    left = DUMP_BYTES
+    for i, name in enumerate(sorted(arrays, key=lambda k: (arrays[k].nbytes, k))):
+        a = arrays[name]
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(20240).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 class KernelProf:
@@ -173,9 +201,23 @@ def run_c5(args):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(x)
+        y = step(x)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"frames": y.cpu().numpy()})      # device fp32 NCHW [B, 3, 2h, 2w]
+    out = {
+        "metric": "upscaled frames/s (inference, generator only) at %s" % ("256->512" if (h, w) == (256, 256) else "%dx%d->%dx%d" % (h, w, 2 * h, 2 * w)),
+        "value": round(B * args.steps / dt, 1), "unit": "frames/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": "C5: make_upscaler_orig((%d,%d,3),k=3,x2,res=%d).predict, BN folded, bf16 NHWC activations, fp32 accumulate, "
+                               "batch %d, one hipGraph replay per batch" % (2 * h, 2 * w, args.res_blocks, B), "global_batch": B,
+                   "frame": "%dx%d->%dx%d" % (h, w, 2 * h, 2 * w), "parallelism": "dp1", "launch": "eager" if args.no_graph else "hipGraph replay"},
+    }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
 
     # dominant kernel: the 64->64 3x3 trunk convolution (2*res+1 launches per batch); HIP events around eager launches
     evs = []
@@ -220,16 +262,7 @@ def run_c5(args):
         tot = st["fetch_bytes_per_step"] + st["write_bytes_per_step"]
         roof["step"] = {"hbm_bytes_per_batch": tot, "hbm_bytes_per_frame": st["bytes_per_frame"], "achieved_gbs": round(tot / (dt / args.steps) / 1e9, 1),
                         "frac_of_hbm_peak": round(tot / (dt / args.steps) / 1e9 / PEAK_HBM_GBS, 4), "source": st.get("source")}
-    out = {
-        "metric": "upscaled frames/s (inference, generator only) at %s" % ("256->512" if (h, w) == (256, 256) else "%dx%d->%dx%d" % (h, w, 2 * h, 2 * w)),
-        "value": round(B * args.steps / dt, 1), "unit": "frames/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-        "config": {"workload": "C5: make_upscaler_orig((%d,%d,3),k=3,x2,res=%d).predict, BN folded, bf16 NHWC activations, fp32 accumulate, "
-                               "batch %d, one hipGraph replay per batch" % (2 * h, 2 * w, args.res_blocks, B), "global_batch": B,
-                   "frame": "%dx%d->%dx%d" % (h, w, 2 * h, 2 * w), "parallelism": "dp1", "launch": "eager" if args.no_graph else "hipGraph replay"},
-        "roofline": roof,
-    }
+    out["roofline"] = roof
     if not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_c5(args, h, w)
     print(json.dumps(out), flush=True)
@@ -261,7 +294,13 @@ def main():
                     help="secondary line, never the headline: the documented fast path without the reference's separate predict-mode "
                          "generator pass (train_gan3.py:346) -- the critic trains on the fakes of the generator's one training-mode forward")
     ap.add_argument("--cpu-sample-batch", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline of the dominant kernel (eager passes after the timed region) and the CPU-oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (losses, trained weights; C5: frames) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config == "c5":
         if args.gpus != 1:
             raise SystemExit("--config c5 is a single-GPU configuration")
@@ -350,24 +389,34 @@ def main():
     bf16_trunk = trunk_dtype != "fp32" and k == 3
     dom_tags = ("trunk_conv", "trunk_conv_dgrad")
     res_tags = ("trunk_conv_res", "trunk_conv_dgrad_res")     # bf16: the launches with a residual input run the v1 kernel
-    if not use_graph:
+    if args.full and not use_graph:
         rt.prof = KernelProf(dom_tags + res_tags)
     if group is not None:
         trainer.coll_prof = {}                  # HIP events around every collective (compute stream: the exposed time)
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     sync()
     t0 = time.perf_counter()
-    marks[0].record()
+    if group is not None:
+        marks[0].record()
     for i in range(args.steps):
         losses = step(lr, hr)
-        marks[i + 1].record()                   # per-step device time of this rank, read after the timed region (no sync inside it)
+        if group is not None:
+            marks[i + 1].record()               # per-step device time of this rank, read after the timed region (no sync inside it)
     sync()
     dt = time.perf_counter() - t0
     prof, rt.prof = rt.prof, None
     coll_prof, trainer.coll_prof = trainer.coll_prof, None
-    step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+    if args.dump_outputs and rank == 0:
+        # what the caller of the step holds after the last timed step: its four losses and the trained models
+        import numpy as np
+        outs = {"losses": np.asarray(losses, np.float64)}
+        for tag, m in (("G", G), ("D", D)):
+            outs[tag + "_params"] = m.ps.params[:m.ps.n_trainable].cpu().numpy()
+            if m.ps.n_state:
+                outs[tag + "_state"] = m.ps.state[:m.ps.n_state].cpu().numpy()
+        dump_outputs(args.dump_outputs, outs)
     roof_note = "HIP events around every launch of the kernel inside the timed region"
-    if use_graph:
+    if args.full and use_graph:
         # kernels inside a graph replay cannot be bracketed one by one: time the same kernel launches with HIP
         # events in eager steps of the same workload right after the timed region
         rt.prof = prof = KernelProf(dom_tags + res_tags)
@@ -384,6 +433,7 @@ def main():
     if group is not None:
         dist.all_reduce(dt_t, op=dist.ReduceOp.MAX, group=group)
         # what makes an N > 1 record explain itself: every rank's step times and the time its compute stream waited at each collective
+        step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
         mine = {"rank": rank, "wall_s": round(dt, 4), "step_ms_min": round(step_ms[0], 3), "step_ms_median": round(step_ms[len(step_ms) // 2], 3),
                 "step_ms_max": round(step_ms[-1], 3),
                 "collectives_ms": {name: round(sum(a.elapsed_time(b) for a, b in ev) / max(len(ev), 1), 4) for name, ev in sorted((coll_prof or {}).items())}}
@@ -402,7 +452,7 @@ def main():
     frames = args.batch * world * args.steps
 
     # roofline of the dominant kernel: the 64->64 trunk convolution (forward and data gradient run the same kernel)
-    mean_ms, launches = prof.mean_ms(dom_tags)
+    mean_ms, launches = prof.mean_ms(dom_tags) if prof is not None else (None, 0)
     flop_per_launch = 2.0 * (64 * 64 * k * k) * (h * w) * args.batch           # 2 * MAC/pixel * pixels * frames
     shape_key = "n%d_%dx%d" % (args.batch, h, w)
     roof = None
@@ -467,15 +517,16 @@ def main():
                        "global_batch": args.batch * world, "frame": "%dx%d->%dx%d" % (h, w, 2 * h, 2 * w),
                        "parallelism": "dp%d" % world, "launch": ("hipGraph replay" if group is None else "%d hipGraphs per step around the RCCL all-reduces" % len(trainer._graph)) if use_graph else "eager"},
             "last_losses": [round(float(v), 6) for v in losses],
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roof
         if dp_info is not None:
             out["data_parallel"] = dp_info
             if world == 1:
                 out["rehearsal"] = "VCG_BENCH_FORCE_GROUP=1: the data-parallel code path over a 1-rank RCCL communicator on one GPU (self-check, not a scaling measurement)"
             if rehearsal:
                 out["rehearsal"] = "VCG_BENCH_REHEARSAL=1: all ranks on ONE GPU, gloo through the host instead of RCCL -- exercises the launcher / multi-graph / reduction logic; its numbers are NOT a scaling measurement"
-        if world == 1 and not args.no_cpu_baseline and args.content == "mse" and w == h:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.content == "mse" and w == h:
             out["cpu_baseline"] = cpu_baseline(args, h, w)
         print(json.dumps(out), flush=True)
     if group is not None:
