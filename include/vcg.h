@@ -299,8 +299,10 @@ int vcg_f32_nchw_to_bf16_nhwc(const void* x, void* y, int32_t n, int32_t c, int3
 int vcg_bf16_nhwc_to_f32_nchw(const void* x, void* y, int32_t n, int32_t c, int32_t h, int32_t w, hipStream_t stream);
 
 /* Conv2D forward on bf16 NHWC (replaces keras Conv2D [+BatchNormalization(inference)+PReLU+Add] at
- * upscaling/upscaler/model.py:19-25,283-285).  Instantiated: 3x3 stride 1 'same' 64->64 (generator trunk);
- * other shapes return VCG_E_UNSUPPORTED. */
+ * upscaling/upscaler/model.py:19-25,283-285).  Instantiated: 3x3 stride 1 'same' 64->64 (generator trunk) and 5x5 stride 1 'same'
+ * 64->64 (the trunk of the reference's default generator, kernel_size=5: model.py:267; run on the generic kernels below, so w_packed is
+ * their fragment layout, vcg_pack_conv_frag_bf16(w, 25, 64, 64, 0, ...); no statistics form: stats_mode != VCG_STATS_NONE returns
+ * VCG_E_UNSUPPORTED); other shapes return VCG_E_UNSUPPORTED. */
 int vcg_conv2d_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* w_packed, void* y, const vcg_epilogue_bf16* ep,
                         hipStream_t stream);
 /* records per group the convolution writes into ep->stats for this shape and mode (> 0), or a negative VCG_E_* when its epilogue
@@ -309,7 +311,9 @@ int vcg_conv2d_bf16_stats_records(const vcg_conv_desc* d, int32_t stats_mode);
 
 /* Conv2DTranspose(strides=2, padding='same') forward on bf16 NHWC (+ fused LeakyReLU: upsampling_block,
  * upscaling/upscaler/model.py:70-75).  w_packed: [tap][out][in] (vcg_pack_conv_kernel_bf16(w, 9, out, in, 0, 0) from
- * Keras' (kh,kw,out,in)).  Instantiated: 3x3, in = 64, out = 64 * {1,2,4,8}; ep may carry shift (the bias) and VCG_ACT_LRELU. */
+ * Keras' (kh,kw,out,in)).  Instantiated: 3x3, in = 64, out = 64 * {1,2,4,8}; ep may carry shift (the bias) and VCG_ACT_LRELU.
+ * (5x5, and 3x3 on 256 input channels -- the up-sampling stages of kernel_size=5 / upscale_factor=4 generators -- run on
+ * vcg_conv_transpose2d_nhwc_bf16_fwd.) */
 int vcg_conv_transpose2d_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* w_packed, void* y, const vcg_epilogue_bf16* ep,
                                   hipStream_t stream);
 

@@ -1,0 +1,211 @@
+"""bf16 inference of make_upscaler_orig models through UpscalerOrig.to_inference_bf16(): by default the reference's own generator
+(kernel_size 5, upscale_factor 4, 16 residual blocks; upscaling/upscaler/model.py:267) at 128 -> 512, batch 32, one hipGraph replay per
+batch.  Prints one JSON line per run, shaped like ``bench.py --config c5``'s.
+
+  --fp32   also times the fp32 product path (G.forward, i.e. what G.predict runs per batch) on the same weights and frames; it may run a
+           smaller batch per call (--fp32-batch), stated in its line
+  --full   per-layer HIP-event times of the bf16 pass (the calls the engine makes, on its buffers), with algorithmic FLOP, TFLOP/s and the
+           share of the 2.5 PFLOP/s dense bf16 peak; for the 5x5 trunk convolution also an A/B, alternated in this process, of
+           vcg_conv2d_bf16_fwd (folded BN + PReLU epilogue) against vcg_conv2d_nhwc_bf16_fwd (bias only) -- the same generic kernels, so the
+           pair prices the epilogue
+
+Usage: python scripts/bench_infer_bf16.py [--lr-size 128] [--lr-width W] [--batch 32] [--kernel-size 5] [--upscale 4] [--res-blocks 16]
+                                          [--steps 10] [--warmup 3] [--fp32] [--full]"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "video-cycle_gan-upscaling_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+PEAK_BF16 = 2.5e15          # MI355X dense bf16 MFMA, FLOP/s
+
+
+# algorithmic FLOP per layer (2 per multiply-add; ISSUE table: 128 -> 512 with the defaults = 372 GFLOP per frame)
+def flop_conv(n, h, w, cin, cout, k):
+    """Conv2D 'same', stride 1: every output pixel sums k*k*cin products per output channel"""
+    return 2.0 * n * h * w * cin * cout * k * k
+
+
+def flop_convt(n, h, w, cin, cout, k):
+    """Conv2DTranspose stride 2 'same' on an h x w input: every input pixel scatters k*k*cout products per input channel"""
+    return 2.0 * n * h * w * cin * cout * k * k
+
+
+def flop_frame(h, w, k, f, res):
+    t = flop_conv(1, h, w, 3, 64, 9) + (2 * res + 1) * flop_conv(1, h, w, 64, 64, k)
+    hh, ww, cin = h, w, 64
+    while f > 1:
+        t += flop_convt(1, hh, ww, cin, 256, k)
+        hh, ww, cin, f = 2 * hh, 2 * ww, 256, f // 2
+    return t + flop_conv(1, hh, ww, 256, 3, 9)
+
+
+def time_events(fn, reps, warm=2):
+    import torch
+    for _ in range(warm):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps          # ms per call
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lr-size", type=int, default=128)
+    ap.add_argument("--lr-width", type=int, default=None)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--kernel-size", type=int, default=5)
+    ap.add_argument("--upscale", type=int, default=4)
+    ap.add_argument("--res-blocks", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--fp32", action="store_true")
+    ap.add_argument("--fp32-batch", type=int, default=4)
+    ap.add_argument("--full", action="store_true")
+    ap.add_argument("--ab-reps", type=int, default=5)
+    args = ap.parse_args()
+
+    import torch
+    from upscaler import _lib as L
+    from upscaler import data as PD
+    from upscaler import model as PM
+
+    h, B, k, f, res = args.lr_size, args.batch, args.kernel_size, args.upscale, args.res_blocks
+    w = args.lr_width or h
+    frame = "%dx%d->%dx%d" % (h, w, f * h, f * w)
+    G = PM.make_upscaler_orig((f * h, f * w, 3), kernel_size=k, upscale_factor=f, res_block_num=res, seed=7)
+    inf = G.to_inference_bf16()
+    rt = inf.rt
+    g1 = torch.Generator().manual_seed(1234)
+    x = PD.frames_u8_to_device(torch.randint(0, 256, (B, h, w, 3), generator=g1, dtype=torch.uint8))
+    inf.capture(B, h, w)
+    for _ in range(args.warmup):
+        inf.replay(x)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        inf.replay(x)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    fl = flop_frame(h, w, k, f, res)
+    bf = {"metric": "upscaled frames/s (inference, generator only, bf16) at %s" % frame, "value": round(B * args.steps / dt, 2),
+          "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+          "higher_is_better": True, "dtype": "bf16", "data": "synthetic",
+          "gflop_per_frame": round(fl / 1e9, 1), "tflops": round(fl * B * args.steps / dt / 1e12, 1),
+          "peak_share": round(fl * B * args.steps / dt / PEAK_BF16, 3),
+          "config": {"workload": "make_upscaler_orig((%d,%d,3),k=%d,x%d,res=%d).to_inference_bf16(), BN folded, bf16 NHWC activations, "
+                                 "fp32 accumulate, batch %d, one hipGraph replay per batch" % (f * h, f * w, k, f, res, B),
+                     "global_batch": B, "frame": frame, "launch": "hipGraph replay"}}
+    print(json.dumps(bf), flush=True)
+
+    if args.fp32:
+        b32 = min(args.fp32_batch, B)
+        xs = x[:b32].contiguous()
+        with torch.no_grad():
+            for _ in range(max(1, args.warmup)):
+                G.forward(xs, training=False)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                G.forward(xs, training=False)
+            torch.cuda.synchronize()
+        d32 = time.perf_counter() - t0
+        fps32 = b32 * args.steps / d32
+        print(json.dumps({"metric": "upscaled frames/s (inference, generator only, fp32 product path) at %s" % frame, "value": round(fps32, 2),
+                          "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+                          "ms_per_step": round(d32 / args.steps * 1e3, 3), "higher_is_better": True, "dtype": "fp32", "data": "synthetic",
+                          "bf16_speedup": round(bf["value"] / fps32, 2),
+                          "config": {"workload": "G.forward(x, training=False) -- what G.predict runs per batch -- same weights and frames, "
+                                                 "batch %d per call (eager launches)" % b32, "global_batch": b32, "frame": frame}}), flush=True)
+
+    if args.full:
+        full(args, inf, x, h, w, k, f, res, B)
+
+
+def full(args, inf, x, h, w, k, f, res, B):
+    """per-layer HIP-event times of the calls the bf16 pass makes; the trunk convolution A/B against the bias-only generic entry point"""
+    import torch
+    from upscaler import _lib as L
+    rt, lib, st = inf.rt, inf.rt.lib, inf.rt.stream
+    Bf = inf._buffers(B, h, w)
+    rows = []
+
+    def row(name, ms, flop, extra=None):
+        d = {"layer": name, "ms": round(ms, 4), "gflop": round(flop / 1e9, 2), "tflops": round(flop / ms / 1e9, 1),
+             "peak_share": round(flop / (ms * 1e-3) / PEAK_BF16, 3)}
+        d.update(extra or {})
+        rows.append(d)
+
+    # initial/conv 9x9 3 -> 64 (+PReLU)
+    w0, b0, a0 = inf.first
+    d0 = L.ConvDesc(B, 3, h, w, 64, h, w, 9, 9, 1, 4, 4)
+    ms = time_events(lambda: L.check(lib.vcg_conv9x9_from3_bf16_fwd(ctypes.byref(d0), x.data_ptr(), w0.data_ptr(), b0.data_ptr(), a0.data_ptr(),
+                                                                    Bf["skip"].data_ptr(), st), "first"), args.ab_reps)
+    row("initial/conv 9x9 3->64", ms, flop_conv(B, h, w, 3, 64, 9))
+    # a trunk convolution (k x k 64 -> 64, BN folded + PReLU) and its A/B against the generic kernel
+    w1, s1, h1, al = inf.trunk[0][:4] if inf.trunk else (inf.prefinal[0], inf.prefinal[1], inf.prefinal[2], None)
+    dk = L.ConvDesc(B, 64, h, w, 64, h, w, k, k, 1, k // 2, k // 2)
+    ep = L.EpilogueBf16(s1.data_ptr(), h1.data_ptr(), L.ACT_PRELU if al is not None else L.ACT_NONE, 0.0, al.data_ptr() if al is not None else None, None)
+    new = lambda: L.check(lib.vcg_conv2d_bf16_fwd(ctypes.byref(dk), Bf["skip"].data_ptr(), w1.data_ptr(), Bf["b"].data_ptr(), ctypes.byref(ep), st), "trunk")
+    c1 = inf.model.blocks[0][0] if inf.model.blocks else inf.model.c_pre
+    wg = torch.empty(k * k * 64 * 64, dtype=torch.bfloat16, device=rt.device)
+    L.check(lib.vcg_pack_conv_frag_bf16(c1.ps[c1.name + "/kernel"].data_ptr(), k * k, 64, 64, 0, wg.data_ptr(), st), "pack frag")
+    gen = lambda: L.check(lib.vcg_conv2d_nhwc_bf16_fwd(ctypes.byref(dk), Bf["skip"].data_ptr(), wg.data_ptr(), h1.data_ptr(), L.ACT_NONE, 0.0,
+                                                       Bf["c"].data_ptr(), st), "trunk generic")
+    ab(rows, "res_block conv %dx%d 64->64 (x%d per pass); A/B arm: bias only, no PReLU" % (k, k, 2 * res + 1), new, gen,
+       flop_conv(B, h, w, 64, 64, k), args.ab_reps)
+    # the up-sampling stages on the engine's chunk of frames, A/B against the generic transposed convolution
+    us = Bf["us"]
+    ch = us[0].shape[0]
+    src, hh, ww = Bf["a"], h, w
+    crop = max(k - 2, 0) // 2
+    for i, ((wt, bt, slope, cin), up, u) in enumerate(zip(inf.ups, inf.model.ups, us)):
+        dt = L.ConvDesc(ch, cin, hh, ww, 256, 2 * hh, 2 * ww, k, k, 2, crop, crop)
+        if inf._generic(up, 0):
+            kern = "generic gconv (vcg_conv_transpose2d_nhwc_bf16_fwd)"
+            call = (lambda dt=dt, s=src, wt=wt, u=u, bt=bt, slope=slope:
+                    L.check(lib.vcg_conv_transpose2d_nhwc_bf16_fwd(ctypes.byref(dt), s.data_ptr(), wt.data_ptr(), bt.data_ptr(), L.ACT_LRELU, slope,
+                                                                   u.data_ptr(), st), "convT generic"))
+        else:
+            kern = "convt3x3_c64_bf16_kernel (vcg_conv_transpose2d_bf16_fwd)"
+            ept = L.EpilogueBf16(None, bt.data_ptr(), L.ACT_LRELU, slope, None, None)
+            call = (lambda dt=dt, s=src, wt=wt, u=u, ept=ept:
+                    L.check(lib.vcg_conv_transpose2d_bf16_fwd(ctypes.byref(dt), s.data_ptr(), wt.data_ptr(), u.data_ptr(), ctypes.byref(ept), st), "convT"))
+        name = "upscaling/%d ConvT %dx%d s2 %d->256 at %dx%d, %d frames per launch" % (i, k, k, cin, 2 * hh, 2 * ww, ch)
+        row(name, time_events(call, args.ab_reps), flop_convt(ch, hh, ww, cin, 256, k), {"kernel": kern})
+        src, hh, ww = u, 2 * hh, 2 * ww
+    wf, bf_ = inf.final
+    df = L.ConvDesc(ch, 256, hh, ww, 3, hh, ww, 9, 9, 1, 4, 4)
+    ms = time_events(lambda: L.check(lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1,
+                                                                  Bf["y"].data_ptr(), st), "final"), args.ab_reps)
+    row("final/conv 9x9 256->3 at %dx%d, %d frames per launch" % (hh, ww, ch), ms, flop_conv(ch, hh, ww, 256, 3, 9))
+    for r in rows:
+        print(json.dumps(dict(r, kind="layer")), flush=True)
+
+
+def ab(rows, name, new, gen, flop, reps):
+    """two arms alternated (A B A B ...), each timed by HIP events; medians"""
+    import statistics
+    tn, tg = [], []
+    for _ in range(3):
+        tn.append(time_events(new, reps))
+        tg.append(time_events(gen, reps))
+    mn, mg = statistics.median(tn), statistics.median(tg)
+    rows.append({"layer": name, "ms": round(mn, 4), "gflop": round(flop / 1e9, 2), "tflops": round(flop / mn / 1e9, 1),
+                 "peak_share": round(flop / (mn * 1e-3) / PEAK_BF16, 3), "generic_ms": round(mg, 4),
+                 "generic_tflops": round(flop / mg / 1e9, 1), "ratio_vs_bias_only": round(mg / mn, 2),
+                 "kernel": "generic gconv with the vcg_epilogue_bf16 terms (vcg_conv2d_bf16_fwd)"})
+
+
+if __name__ == "__main__":
+    main()

@@ -1662,6 +1662,9 @@ int vcg_bf16_nhwc_to_f32_nchw(const void* x, void* y, int32_t n, int32_t c, int3
 
 // the v2 kernel finds its halo rows through 32-bit byte offsets against the image's buffer descriptor: the image plus the halo rows
 // below it (and a row of slack for the wrapped offsets of the row above it) must stay below 4 GiB, or a halo offset wraps into the image
+// bf16_gconv.hip: the 5x5 trunk convolution on the generic kernels, with this file's epilogue contract
+int vcg_gconv5x5_c64_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* wfrag, void* y, const vcg_epilogue_bf16* ep, hipStream_t stream);
+
 static bool v2_image_fits(int h, int w) { return ((long)h + V2_HR + 2) * w * 128 + 4096 <= 0xFFFFFFE0l; }
 
 int vcg_conv2d_bf16_stats_records(const vcg_conv_desc* d, int32_t stats_mode) {
@@ -1764,6 +1767,12 @@ int vcg_conv2d_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* w_pac
 #undef VCG_C3_LAUNCH
         VCG_LAUNCH_CHECK();
         return VCG_OK;
+    }
+    if (d->cin == 64 && d->cout == 64 && d->kh == 5 && d->kw == 5 && d->stride == 1 && d->pad_top == 2 && d->pad_left == 2) {
+        // 5x5 trunk of the reference's default generator: the generic kernels' plan (bf16_gconv.hip), w_packed in their fragment layout;
+        // no statistics form
+        if (ep && ep->stats_mode != VCG_STATS_NONE) return VCG_E_UNSUPPORTED;
+        return vcg_gconv5x5_c64_bf16_fwd(d, x, w_packed, y, ep, stream);
     }
     return VCG_E_UNSUPPORTED;
 }

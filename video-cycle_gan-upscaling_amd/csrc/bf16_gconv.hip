@@ -32,6 +32,11 @@ struct GcParams {
     void* y;                // bf16 NHWC [n][oh][ow][mch]
     const float* bias;      // [mch] or null
     const void* mask_src;   // optional bf16 NHWC tensor of the output's shape: out *= (mask_src > 0 ? 1 : mask_slope)
+    // optional vcg_epilogue_bf16 terms (the 5x5 trunk convolution of vcg_conv2d_bf16_fwd): out = act(acc * scale + bias) + res, act's
+    // negative-side slope prelu[c] where given; all null elsewhere (the arithmetic of the other layers is unchanged)
+    const float* scale;
+    const float* prelu;
+    const void* res;
     size_t wbytes;
     int n, ih, iw, kch;     // input tensor
     int oh, ow, mch;        // output tensor
@@ -56,7 +61,9 @@ __device__ __forceinline__ bf16x8 ld_frag(vcg_rsrc r, unsigned off) {
 }
 
 // workgroup = 4 waves; wave = 64 output channels (2 MFMA row blocks) x NT tiles of 32 consecutive logical pixels
-template <int NT>
+// EPI: the vcg_epilogue_bf16 terms (scale, per-channel PReLU slope, residual) -- a separate instantiation, so the layers that do not
+// use them keep their code
+template <int NT, bool EPI = false>
 __global__ __launch_bounds__(256, (NT == 4 ? 2 : 4)) void gconv_bf16_kernel(const GcParams p) {
     const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -157,14 +164,24 @@ __global__ __launch_bounds__(256, (NT == 4 ? 2 : 4)) void gconv_bf16_kernel(cons
                     v[4 + j] = hi;
                 }
                 if (!ok || (m == 1 && !two)) continue;
-                bf16x8 mk;
+                bf16x8 mk, rs;
                 if (p.mask_src) mk = *(const bf16x8*)((const __bf16*)p.mask_src + obase + co);
+                if (EPI && p.res) rs = *(const bf16x8*)((const __bf16*)p.res + obase + co);
                 bf16x8 o;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    float u = v[j] + (p.bias ? p.bias[co + j] : 0.f);
-                    u = u >= 0.f ? u : u * slope;
+                    float u;
+                    if constexpr (EPI) {
+                        const float b = p.bias ? p.bias[co + j] : 0.f;
+                        u = p.scale ? fmaf(v[j], p.scale[co + j], b) : v[j] + b;
+                        const float sl = p.prelu ? p.prelu[co + j] : slope;
+                        u = u >= 0.f ? u : u * sl;
+                    } else {
+                        u = v[j] + (p.bias ? p.bias[co + j] : 0.f);
+                        u = u >= 0.f ? u : u * slope;
+                    }
                     if (p.mask_src) u *= ((float)mk[j] > 0.f ? 1.f : p.mask_slope);
+                    if (EPI && p.res) u += (float)rs[j];
                     o[j] = (__bf16)u;
                 }
                 *(bf16x8*)((__bf16*)p.y + obase + co) = o;
@@ -195,6 +212,9 @@ struct GlParams {
     void* y;                // bf16 NHWC [n][oh][ow][mch]
     const float* bias;
     const void* mask_src;
+    const float* scale;
+    const float* prelu;
+    const void* res;
     size_t wbytes;
     int n, ih, iw, kch, oh, ow, mch, loh, low, osy, osx, ooy, oox, mblocks, act;
     float alpha, mask_slope;
@@ -227,7 +247,7 @@ __device__ __forceinline__ void gl_barrier() {
 // halo pieces only, which also lets them run a ring of THREE stages (two entries in flight; the same ring in the one-role form was
 // measured slower, profiles/r03_gconv_ring_ab.txt).  What it serves: the transposed convolution's data gradient -- 36 MFMAs per wave and
 // entry over a 1.07 GB tensor -- and the 64-channel data gradients of the critics.
-template <int SP, bool HALF>
+template <int SP, bool HALF, bool EPI = false>
 __global__ __launch_bounds__(HALF ? 512 : 256, 1) void gconv_lds_bf16_kernel(const GlParams p) {
     constexpr int TRW = HALF ? GL_TR / 2 : GL_TR;                // output rows per wave
     constexpr int HR = GL_TR + SP, HC = GL_TC + SP, ROWB = HC * 128, XB = HR * ROWB, CH16 = XB / 16;
@@ -380,13 +400,20 @@ __global__ __launch_bounds__(HALF ? 512 : 256, 1) void gconv_lds_bf16_kernel(con
             const float slope = p.act == VCG_ACT_LRELU ? p.alpha : 1.f;
             const vcg_rsrc ry = make_rsrc((unsigned char*)p.y + cur.img * img_out, (unsigned long)img_out);
             const vcg_rsrc rm = make_rsrc((const unsigned char*)p.mask_src + cur.img * img_out, (unsigned long)(p.mask_src ? img_out : 0));
+            const vcg_rsrc rr = make_rsrc((const unsigned char*)p.res + cur.img * img_out, (unsigned long)(EPI && p.res ? img_out : 0));
             const int lx = cur.tx * GL_TC + r, ox = lx * p.osx + p.ph[cur.ph].oox;
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int co = mtile * 32 + 16 * q + 8 * hh;
-                float bs[8];
+                float bs[8], sc[8], sl[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) bs[j] = p.bias && mtile < p.mblocks ? p.bias[co + j] : 0.f;
+                for (int j = 0; j < 8; ++j) {
+                    bs[j] = p.bias && mtile < p.mblocks ? p.bias[co + j] : 0.f;
+                    if constexpr (EPI) {
+                        sc[j] = p.scale && mtile < p.mblocks ? p.scale[co + j] : 1.f;
+                        sl[j] = p.prelu && mtile < p.mblocks ? p.prelu[co + j] : slope;
+                    }
+                }
 #pragma unroll
                 for (int n = 0; n < TRW; ++n) {
                     const int ly = cur.ty * GL_TR + r0 + n, oy = ly * p.osy + p.ph[cur.ph].ooy;
@@ -402,14 +429,22 @@ __global__ __launch_bounds__(HALF ? 512 : 256, 1) void gconv_lds_bf16_kernel(con
                         v[j] = lo;
                         v[4 + j] = hi;
                     }
-                    bf16x8 mk;
+                    bf16x8 mk, rs;
                     if (p.mask_src) mk = ld_frag(rm, off);
+                    if (EPI && p.res) rs = ld_frag(rr, off);
                     bf16x8 o;
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
-                        float u = v[j] + bs[j];
-                        u = u >= 0.f ? u : u * slope;
+                        float u;
+                        if constexpr (EPI) {
+                            u = p.scale ? fmaf(v[j], sc[j], bs[j]) : v[j] + bs[j];
+                            u = u >= 0.f ? u : u * sl[j];
+                        } else {
+                            u = v[j] + bs[j];
+                            u = u >= 0.f ? u : u * slope;
+                        }
                         if (p.mask_src) u *= ((float)mk[j] > 0.f ? 1.f : p.mask_slope);
+                        if (EPI && p.res) u += (float)rs[j];
                         o[j] = (__bf16)u;
                     }
                     const u32x4 ob = __builtin_bit_cast(u32x4, o);
@@ -500,16 +535,16 @@ __global__ void f32_to_bf16_kernel(const float* __restrict__ x, __bf16* __restri
     if (i < count) y[i] = (__bf16)x[i];
 }
 
-template <int SP, bool HALF>
+template <int SP, bool HALF, bool EPI = false>
 int launch_gconv_lds_sp(const GlParams& q, int grid, hipStream_t st) {
     constexpr int HR = GL_TR + SP, HC = GL_TC + SP, CH16 = HR * HC * 8, NDMA = (CH16 + 255) / 256, LDS = (HALF && 3 * NDMA * 4096 <= 160 * 1024 ? 3 : 2) * NDMA * 4096;
     static bool attr = false;
     if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)gconv_lds_bf16_kernel<SP, HALF>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        hipError_t e = hipFuncSetAttribute((const void*)gconv_lds_bf16_kernel<SP, HALF, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         if (e != hipSuccess) return (int)e;
         attr = true;
     }
-    hipLaunchKernelGGL((gconv_lds_bf16_kernel<SP, HALF>), dim3(grid), dim3(HALF ? 512 : 256), LDS, st, q);
+    hipLaunchKernelGGL((gconv_lds_bf16_kernel<SP, HALF, EPI>), dim3(grid), dim3(HALF ? 512 : 256), LDS, st, q);
     VCG_LAUNCH_CHECK();
     return VCG_OK;
 }
@@ -554,6 +589,7 @@ bool plan_gconv_lds(const GcParams& p, GlParams& q, int& spe_out, bool& half_out
         }
     }
     q.x = p.x; q.wf = p.wf; q.y = p.y; q.bias = p.bias; q.mask_src = p.mask_src; q.wbytes = p.wbytes;
+    q.scale = p.scale; q.prelu = p.prelu; q.res = p.res;
     q.n = p.n; q.ih = p.ih; q.iw = p.iw; q.kch = p.kch; q.oh = p.oh; q.ow = p.ow; q.mch = p.mch; q.loh = p.loh; q.low = p.low;
     q.osy = p.osy; q.osx = p.osx; q.ooy = p.ooy; q.oox = p.oox; q.mblocks = p.mblocks; q.act = p.act; q.alpha = p.alpha; q.mask_slope = p.mask_slope;
     q.isy = p.isy; q.isx = p.isx; q.stats = p.stats;
@@ -571,6 +607,8 @@ bool plan_gconv_lds(const GcParams& p, GlParams& q, int& spe_out, bool& half_out
 
 int launch_gconv_lds(const GlParams& q, int spe, bool half, hipStream_t st) {
     const int grid = q.pairs < 256 ? q.pairs : 256;
+    if (q.scale || q.prelu || q.res)                           // the epilogue terms: instantiated for the 5x5 trunk convolution's plan only
+        return spe == 4 && !half ? launch_gconv_lds_sp<4, false, true>(q, grid, st) : VCG_E_UNSUPPORTED;
     switch (spe) {
         case 1: return half ? launch_gconv_lds_sp<1, true>(q, grid, st) : launch_gconv_lds_sp<1, false>(q, grid, st);
         case 2: return half ? launch_gconv_lds_sp<2, true>(q, grid, st) : launch_gconv_lds_sp<2, false>(q, grid, st);
@@ -639,7 +677,11 @@ int launch_gconv(GcParams& p, hipStream_t st) {
     const long wgs = (tiles + 4 * nt - 1) / (4 * nt);
     if (wgs > 0x7fffffffL) return VCG_E_SHAPE;
     const dim3 grid((unsigned)wgs, (unsigned)mgroups);
-    if (big) hipLaunchKernelGGL(gconv_bf16_kernel<4>, grid, dim3(256), 0, st, p);
+    const bool epi = p.scale || p.prelu || p.res;
+    if (epi) {
+        if (big) hipLaunchKernelGGL((gconv_bf16_kernel<4, true>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((gconv_bf16_kernel<2, true>), grid, dim3(256), 0, st, p);
+    } else if (big) hipLaunchKernelGGL(gconv_bf16_kernel<4>, grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL(gconv_bf16_kernel<2>, grid, dim3(256), 0, st, p);
     VCG_LAUNCH_CHECK();
     return VCG_OK;
@@ -761,6 +803,25 @@ int vcg_conv2d_nhwc_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* 
     p.act = act; p.alpha = act_alpha;
     for (int ky = 0; ky < d->kh; ++ky)
         for (int kx = 0; kx < d->kw; ++kx) p.taps[p.ntaps++] = GcTap{(short)(ky - d->pad_top), (short)(kx - d->pad_left), (short)(ky * d->kw + kx), 0};
+    return launch_gconv(p, stream);
+}
+
+// the 5x5 stride-1 'same' 64 -> 64 trunk convolution of vcg_conv2d_bf16_fwd (kernel_size=5 generators, model.py:19-25,283-285) on this
+// file's kernels, with the vcg_epilogue_bf16 terms: y = act(acc * scale + shift) + residual, act none / LeakyReLU / PReLU.  The caller has
+// checked the shape and the activation; wfrag = vcg_pack_conv_frag_bf16(w, 25, 64, 64, 0, ...).
+int vcg_gconv5x5_c64_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* wfrag, void* y, const vcg_epilogue_bf16* ep, hipStream_t stream) {
+    int rc = check_gdesc(d);
+    if (rc) return rc;
+    GcParams p{};
+    p.x = x; p.wf = wfrag; p.y = y;
+    fwd_params(d, p);
+    p.bias = ep ? (const float*)ep->shift : nullptr;
+    p.scale = ep ? (const float*)ep->scale : nullptr;
+    p.act = ep ? ep->act : VCG_ACT_NONE;
+    p.alpha = ep ? ep->act_alpha : 0.f;
+    p.prelu = p.act == VCG_ACT_PRELU ? (const float*)ep->prelu_alpha : nullptr;
+    if (p.act == VCG_ACT_PRELU) p.act = VCG_ACT_LRELU;          // the epilogue's negative-side slope is then prelu[c]
+    p.res = ep ? ep->residual : nullptr;
     return launch_gconv(p, stream);
 }
 

@@ -1,8 +1,9 @@
 """Inference-only generator on the bf16-storage kernels (BASELINE.json config C5: "inference-only generator,
 batch=32 256->512 bf16, hipGraph-captured per-frame step").
 
-Serves ``make_upscaler_orig`` models (upscaling/upscaler/model.py:267-295) with kernel_size 3, 64 filters and
-upscale_factor 2 -- the topology BASELINE.json's configs name.  What the reference does per call is
+Serves ``make_upscaler_orig`` models (upscaling/upscaler/model.py:267-295) with 64 filters on RGB frames, kernel_size 3 or 5
+and any power-of-two upscale_factor: BASELINE.json's configs (kernel_size 3, x2) and the reference's own defaults (kernel_size 5,
+x4, 16 residual blocks; model.py:267, its CLI's -k 5 -u 4).  What the reference does per call is
 ``upscaler.predict(batch)`` (upscaling/upscaler/data.py:358-363, train_gan3.py:346): a forward pass with the
 BatchNormalization layers in inference mode.  Here that pass is
 
@@ -13,7 +14,10 @@ BatchNormalization layers in inference mode.  Here that pass is
     upsampling: ConvT 3x3 s2 64->256 + LReLU  vcg_conv_transpose2d_bf16_fwd
     final/conv 9x9 256->3 + tanh              vcg_conv9x9_to3_bf16_fwd (fp32 NCHW out)
 
-22 launches, recorded once per input shape into a hipGraph and replayed per batch.  Activations are bf16 NHWC,
+The 5x5 trunk convolutions run on the same entry point (the generic kernels' plan, weights as their MFMA fragments), and the
+up-sampling stages that convt3x3_c64 does not serve -- 5x5, and 3x3 on 256 channels -- on vcg_conv_transpose2d_nhwc_bf16_fwd,
+one per stage (64->256, then 256->256).  22 launches for the k3 x2
+topology, recorded once per input shape into a hipGraph and replayed per batch.  Activations are bf16 NHWC,
 accumulation and the epilogue arithmetic fp32; the weights are rounded to bf16 once, when the engine is built or
 ``refresh()`` is called after a weight update.  The folded BatchNormalization parameters
 (scale = gamma / sqrt(moving_var + 1e-3), shift = (bias - moving_mean) * scale + beta) are 64-element fp32 vectors
@@ -36,9 +40,15 @@ class Bf16Generator:
         if not isinstance(model, UpscalerOrig):
             raise TypeError("Bf16Generator serves make_upscaler_orig models")
         c1 = model.blocks[0][0] if model.blocks else model.c_pre
-        if c1.k != 3 or c1.cin != 64 or c1.cout != 64 or model.upscale_times != 1 or model.c_init.cin != 3:
-            raise NotImplementedError("bf16 inference is instantiated for kernel_size=3, filters=64, upscale_factor=2 "
-                                      "(the topology of BASELINE.json's configs); use model.predict for other shapes")
+        if c1.cin != 64 or c1.cout != 64 or model.c_init.cin != 3:
+            raise NotImplementedError("bf16 inference is instantiated for filters=64 on 3-channel (RGB) frames; "
+                                      "use model.predict for other shapes")
+        if c1.k not in (3, 5) or model.upscale_times < 1:
+            raise NotImplementedError("bf16 inference is instantiated for kernel_size 3 or 5 and upscale_factor >= 2; "
+                                      "use model.predict for other shapes")
+        self.k = c1.k
+        # the k3 x2 topology keeps its launch sequence exactly (BASELINE.json C5); the others chunk the tail by the 4 GiB rule
+        self.legacy = self.k == 3 and model.upscale_times == 1
         self.instance = model.n_pre.norm == "instance"        # per-image statistics cannot be folded: bf16 norm kernels
         self.model = model
         self.rt = model.rt
@@ -47,12 +57,24 @@ class Bf16Generator:
         self.refresh()
 
     # ---- parameters ------------------------------------------------------------------------------------------
-    def _pack3x3(self, conv, transpose):
-        rt = self.rt
-        out = torch.empty(9, conv.cout, conv.cin, dtype=torch.bfloat16, device=rt.device)
-        L.check(rt.lib.vcg_pack_conv_kernel_bf16(conv.ps[conv.name + "/kernel"].data_ptr(), 9, conv.cout, conv.cin, transpose, 0,
+    def _pack(self, conv, transpose):
+        """3x3 layers of the k3 topology: [tap][out][in] bf16 (Conv2D (k,k,in,out) with transpose=1, Conv2DTranspose (k,k,out,in) with
+        transpose=0); every other layer: the generic kernels' MFMA fragments (vcg_pack_conv_frag_bf16: mode 0 for a Conv2D, mode 1 for a
+        Conv2DTranspose, whose kernel is the data gradient's of a stride-2 Conv2D)"""
+        rt, taps = self.rt, conv.k * conv.k
+        out = torch.empty(taps, conv.cout, conv.cin, dtype=torch.bfloat16, device=rt.device)
+        if self._generic(conv, transpose):
+            L.check(rt.lib.vcg_pack_conv_frag_bf16(conv.ps[conv.name + "/kernel"].data_ptr(), taps, conv.cout, conv.cin, 1 - transpose,
+                                                   out.data_ptr(), rt.stream), "vcg_pack_conv_frag_bf16")
+            return out
+        L.check(rt.lib.vcg_pack_conv_kernel_bf16(conv.ps[conv.name + "/kernel"].data_ptr(), taps, conv.cout, conv.cin, transpose, 0,
                                                  out.data_ptr(), rt.stream), "vcg_pack_conv_kernel_bf16")
         return out
+
+    @staticmethod
+    def _generic(conv, transpose):
+        """True where the layer runs on the generic kernels: a 5x5 layer, or a transposed one on more than 64 input channels"""
+        return conv.k != 3 or (not transpose and conv.cin != 64)
 
     def _fold(self, conv, norm):
         """scale = gamma / sqrt(moving_var + eps), shift = (bias - moving_mean) * scale + beta, by the same kernels the
@@ -76,14 +98,12 @@ class Bf16Generator:
         for (c1, n1, c2, n2) in m.blocks:
             s1, h1 = self._fold(c1, n1)
             s2, h2 = self._fold(c2, n2)
-            self.trunk.append((self._pack3x3(c1, 1), s1, h1, c1.ps[n1.prelu_name + "/alpha"], self._pack3x3(c2, 1), s2, h2))
+            self.trunk.append((self._pack(c1, 1), s1, h1, c1.ps[n1.prelu_name + "/alpha"], self._pack(c2, 1), s2, h2))
         sp, hp = self._fold(m.c_pre, m.n_pre)
-        self.prefinal = (self._pack3x3(m.c_pre, 1), sp, hp)
-        up = m.ups[0]
-        wt = torch.empty(9, up.cout, up.cin, dtype=torch.bfloat16, device=rt.device)
-        L.check(rt.lib.vcg_pack_conv_kernel_bf16(up.ps[up.name + "/kernel"].data_ptr(), 9, up.cout, up.cin, 0, 0, wt.data_ptr(),
-                                                 rt.stream), "vcg_pack_conv_kernel_bf16")
-        self.up = (wt, up.ps[up.name + "/bias"], float(up.alpha))
+        self.prefinal = (self._pack(m.c_pre, 1), sp, hp)
+        # one weight set per up-sampling stage: 64 -> 256, then 256 -> 256 (model.py:286-288)
+        self.ups = [(self._pack(up, 0), up.ps[up.name + "/bias"], float(up.alpha), up.cin) for up in m.ups]
+        self.up = self.ups[0][:3]
         wf = torch.empty(L.FINAL9X9_WFRAG_BYTES, dtype=torch.uint8, device=rt.device)
         L.check(rt.lib.vcg_pack_final9x9_bf16(m.c_fin.ps[m.c_fin.name + "/kernel"].data_ptr(), wf.data_ptr(), rt.stream),
                 "vcg_pack_final9x9_bf16")
@@ -100,22 +120,37 @@ class Bf16Generator:
         if key not in self._bufs:
             dev = self.rt.device
             bf = lambda c, hh, ww: torch.empty(n, hh, ww, c, dtype=torch.bfloat16, device=dev)
+            ch = self._tail_chunk(n, h, w)
+            f = 2 ** len(self.ups)
+            # one bf16 NHWC buffer per up-sampling stage: [ch, 2h, 2w, 256], [ch, 4h, 4w, 256], ...
+            us = [torch.empty(ch, 2 ** (s + 1) * h, 2 ** (s + 1) * w, 256, dtype=torch.bfloat16, device=dev) for s in range(len(self.ups))]
             self._bufs[key] = {"skip": bf(64, h, w),
                                "a": bf(64, h, w), "b": bf(64, h, w), "c": bf(64, h, w),
-                               "u": torch.empty(self._tail_chunk(n, h, w), 2 * h, 2 * w, 256, dtype=torch.bfloat16, device=dev),
+                               "u": us[0], "us": us,
                                "z": bf(64, h, w) if self.instance else None,
                                "stats": torch.empty(5, n * 64, dtype=torch.float32, device=dev) if self.instance else None,
-                               "y": torch.empty(n, 3, 2 * h, 2 * w, dtype=torch.float32, device=dev)}
+                               "y": torch.empty(n, 3, f * h, f * w, dtype=torch.float32, device=dev)}
         return self._bufs[key]
 
     def _tail_chunk(self, n, h, w):
-        return E.tail_chunk(n, h, w)
+        """frames per launch of the up-sampling stages and final/conv.  Beyond the k3 x2 topology, a launch's largest tensor (the
+        last stage's output, 2 * 256 bytes per pixel) stays below 4 GiB: the kernels' offsets are 32-bit inside an image, and final/conv's
+        descriptor covers the whole launch"""
+        ch = E.tail_chunk(n, h, w)
+        if self.legacy:
+            return ch
+        f = 2 ** len(self.ups)
+        per = f * f * h * w * 256 * 2
+        ch = max(1, min(ch, 0xFFFFFFE0 // per))
+        launches = -(-n // ch)
+        return -(-n // launches)                 # the same number of launches, frames spread evenly (32 -> 16 + 16, not 31 + 1)
 
     def _conv(self, x, w, y, scale, shift, act, alpha, res, n, h, wd):
         rt = self.rt
         if self.instance:
             return self._conv_instance_norm(x, w, y, shift, act, alpha, res, n, h, wd)
-        d = L.ConvDesc(n, 64, h, wd, 64, h, wd, 3, 3, 1, 1, 1)
+        k = self.k
+        d = L.ConvDesc(n, 64, h, wd, 64, h, wd, k, k, 1, k // 2, k // 2)
         ep = L.EpilogueBf16(scale.data_ptr(), shift.data_ptr(), act, 0.0, alpha.data_ptr() if alpha is not None else None,
                             res.data_ptr() if res is not None else None)
         L.check(rt.lib.vcg_conv2d_bf16_fwd(ctypes.byref(d), x.data_ptr(), w.data_ptr(), y.data_ptr(), ctypes.byref(ep), rt.stream),
@@ -125,7 +160,8 @@ class Bf16Generator:
         """conv (+bias) -> per-image statistics -> normalise + activation + Add, all on bf16 NHWC"""
         rt = self.rt
         z = self._buffers(n, h, wd)["z"]
-        d = L.ConvDesc(n, 64, h, wd, 64, h, wd, 3, 3, 1, 1, 1)
+        k = self.k
+        d = L.ConvDesc(n, 64, h, wd, 64, h, wd, k, k, 1, k // 2, k // 2)
         ep = L.EpilogueBf16(None, bias.data_ptr(), L.ACT_NONE, 0.0, None, None)
         L.check(rt.lib.vcg_conv2d_bf16_fwd(ctypes.byref(d), x.data_ptr(), w.data_ptr(), z.data_ptr(), ctypes.byref(ep), rt.stream),
                 "vcg_conv2d_bf16_fwd")
@@ -142,7 +178,7 @@ class Bf16Generator:
                 "vcg_norm_act_fwd_bf16")
 
     def forward(self, x):
-        """x: device fp32 NCHW [n,3,h,w] in [-1,1] -> device fp32 NCHW [n,3,2h,2w] (buffer owned by the engine)"""
+        """x: device fp32 NCHW [n,3,h,w] in [-1,1] -> device fp32 NCHW [n,3,f*h,f*w] (f = upscale_factor; buffer owned by the engine)"""
         rt, m = self.rt, self.model
         n, _, h, w = x.shape
         B = self._buffers(n, h, w)
@@ -159,18 +195,25 @@ class Bf16Generator:
         wp, sp, hp = self.prefinal
         out = B["a"] if cur is not B["a"] else B["c"]
         self._conv(cur, wp, out, sp, hp, L.ACT_NONE, None, B["skip"], n, h, w)
-        wt, bt, slope = self.up
         wf, bf_ = self.final
-        ept = L.EpilogueBf16(None, bt.data_ptr(), L.ACT_LRELU, slope, None, None)
-        u, y = B["u"], B["y"]
-        ch = u.shape[0]
+        k, crop = self.k, max(self.k - 2, 0) // 2           # TF-SAME crop of Conv2DTranspose(k, strides 2): k3 (0, 1), k5 (1, 2)
+        us, y = B["us"], B["y"]
+        ch = us[0].shape[0]
         for i in range(0, n, ch):
             c = min(ch, n - i)
-            dt = L.ConvDesc(c, 64, h, w, 256, 2 * h, 2 * w, 3, 3, 2, 0, 0)
-            L.check(rt.lib.vcg_conv_transpose2d_bf16_fwd(ctypes.byref(dt), out[i:i + c].data_ptr(), wt.data_ptr(), u.data_ptr(), ctypes.byref(ept),
-                                                         rt.stream), "vcg_conv_transpose2d_bf16_fwd")
-            df = L.ConvDesc(c, 256, 2 * h, 2 * w, 3, 2 * h, 2 * w, 9, 9, 1, 4, 4)
-            L.check(rt.lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(df), u.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, y[i:i + c].data_ptr(),
+            src, hh, ww = out[i:i + c], h, w
+            for (wt, bt, slope, cin), up, u in zip(self.ups, m.ups, us):
+                dt = L.ConvDesc(c, cin, hh, ww, 256, 2 * hh, 2 * ww, k, k, 2, crop, crop)
+                if self._generic(up, 0):
+                    L.check(rt.lib.vcg_conv_transpose2d_nhwc_bf16_fwd(ctypes.byref(dt), src.data_ptr(), wt.data_ptr(), bt.data_ptr(), L.ACT_LRELU,
+                                                                      slope, u.data_ptr(), rt.stream), "vcg_conv_transpose2d_nhwc_bf16_fwd")
+                else:
+                    ept = L.EpilogueBf16(None, bt.data_ptr(), L.ACT_LRELU, slope, None, None)
+                    L.check(rt.lib.vcg_conv_transpose2d_bf16_fwd(ctypes.byref(dt), src.data_ptr(), wt.data_ptr(), u.data_ptr(), ctypes.byref(ept),
+                                                                 rt.stream), "vcg_conv_transpose2d_bf16_fwd")
+                src, hh, ww = u, 2 * hh, 2 * ww
+            df = L.ConvDesc(c, 256, hh, ww, 3, hh, ww, 9, 9, 1, 4, 4)
+            L.check(rt.lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, y[i:i + c].data_ptr(),
                                                     rt.stream), "vcg_conv9x9_to3_bf16_fwd")
         return B["y"]
 
