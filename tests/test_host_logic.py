@@ -67,6 +67,43 @@ def test_workspace_queries_and_argument_errors_without_gpu(built):
         built.check(-2, "x")
 
 
+def test_stats_records_ignore_the_environment(built):
+    """the record count a caller allocates for comes from the shape alone: the library reads no environment variable (the variable
+    below once forced the v1 trunk kernel, which has no statistics epilogue, in this entry point on every call)"""
+    import ctypes
+    lib = built.load()
+    d = built.ConvDesc(8, 64, 256, 256, 64, 256, 256, 3, 3, 1, 1, 1)
+    plain = lib.vcg_conv2d_bf16_stats_records(ctypes.byref(d), built.STATS_BATCH)
+    assert plain > 0
+    saved = os.environ.get("VCG_CONV3X3_V1")
+    os.environ["VCG_CONV3X3_V1"] = "1"
+    try:
+        forced = lib.vcg_conv2d_bf16_stats_records(ctypes.byref(d), built.STATS_BATCH)
+    finally:
+        if saved is None:
+            del os.environ["VCG_CONV3X3_V1"]
+        else:
+            os.environ["VCG_CONV3X3_V1"] = saved
+    assert forced == plain
+
+
+def test_no_environment_switches_in_library_or_package(built):
+    """libvcg_hip.so does not import getenv, and the Python package selects no code path by a VCG_* environment variable"""
+    built.load()
+    nm = subprocess.run(["nm", "-D", "--undefined-only", built.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    undefined = [line.split()[-1] for line in nm.splitlines() if line.strip()]
+    assert undefined, "nm listed no undefined dynamic symbols"
+    assert [u for u in undefined if u == "getenv" or u.startswith("getenv@")] == []
+    pkg = os.path.join(PKG, "upscaler")
+    hits = []
+    for name in sorted(os.listdir(pkg)):
+        if name.endswith(".py"):
+            for i, line in enumerate(open(os.path.join(pkg, name)), 1):
+                if re.search(r"environ.*VCG_", line):
+                    hits.append("%s:%d" % (name, i))
+    assert hits == []
+
+
 def test_reference_signatures_are_mirrored():
     from upscaler import model as PM
 

@@ -1,4 +1,5 @@
 """Build libvcg_hip.so (gfx950) in-tree with hipcc.  Usage: python build.py [--force]"""
+import glob
 import os
 import subprocess
 import sys
@@ -29,7 +30,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=True):
     hipcc = _hipcc()
-    hdrs = [os.path.join(CSRC, "vcg_common.hpp"), os.path.join(ROOT, "include", "vcg.h")]
+    hdrs = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(ROOT, "include", "vcg.h")]
     objs, jobs = [], []
     os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
     for s in SOURCES:

@@ -9,37 +9,12 @@
 // with the inference-mode BatchNormalization folded into a per-channel scale/shift (model.py:20,23,284),
 // PReLU (model.py:21) and the block's Add (model.py:25,285) fused into the epilogue.
 #include "vcg_common.hpp"
-#include <cstdlib>
-#include <utility>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
     // lane l (r = l&31, h = l>>5): A[row r][k = 8h+j], B[k = 8h+j][col r], j = 0..7; D as the f32 form
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// v_permlane32_swap: lanes 32-63 of a <-> lanes 0-31 of b
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void swap32(float& a, float& b) {
-    const u32x2 sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    a = __uint_as_float(sw.x);
-    b = __uint_as_float(sw.y);
-}
-
-// compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N-1>{})
-template <class F, int... Is>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
-    (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -245,13 +220,6 @@ struct C3Params {
     float* stats;            // v2 with STATS: per-channel sum / sum of squares of the stored (bf16-rounded) output, [unit][row group][2][64]
     int stats_per_tile;      // 0: unit = workgroup (one record pair per launch: batch statistics); 1: unit = tile (instance norm)
 };
-
-// workgroup barrier ordering LDS only: global stores stay in flight across it
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 template <bool AFF, bool SLOPE, bool RES>
 __global__ __launch_bounds__(NT, 1) void conv3x3_c64_bf16_kernel(C3Params p) {
@@ -813,8 +781,9 @@ struct I9Params {
 
 // Several workgroups write different 128-byte channel blocks of the SAME pixels (cout = 64 nblk): mapped so that the nblk workgroups of one
 // tile stream sit on ONE XCD (workgroups b and b + 8 share an XCD under round-robin placement -- speed only, never correctness) and run side by
-// side, their pieces of a pixel's 128 nblk bytes meet in that XCD's L2 and leave it together.  An experiment (VCG_XCD_GROUP=1), measured
-// neutral: convT 389 vs 387 us, the final-conv data gradient 717 vs 712 us at C3's shard -- the default is the plain b % nblk mapping.
+// side, their pieces of a pixel's 128 nblk bytes meet in that XCD's L2 and leave it together.  An experiment (xcd_group = 1, which no
+// caller sets any more), measured neutral (profiles/r03_xcd_group_ab.txt): convT 389 vs 387 us, the final-conv data gradient 717 vs 712 us
+// at C3's shard -- the default is the plain b % nblk mapping.
 __device__ __forceinline__ void block_and_stream(int nblk, int xcd_group, int& cb, int& wg) {
     const int b = blockIdx.x;
     if (xcd_group && gridDim.x % (8 * nblk) == 0) {
@@ -1348,6 +1317,7 @@ __global__ __launch_bounds__(NT, 1) void convt3x3_c64_bf16_kernel(CTParams p) {
 constexpr int F_PIX = 72;                    // 64 output columns + 4 + 4
 constexpr int F_ROWB = F_PIX * 128;          // one wave's slice of one input row in LDS (9216 B)
 constexpr int F_LDS = 4 * 2 * F_ROWB + 2 * 4 * 3 * 64 * 4;
+constexpr int F9_MAX_GRID = 512;             // workgroups of one launch: two per CU
 constexpr int F_NFRAG = 4 * 9 * 4 * 64;      // 16-byte weight fragments; the packed buffer holds 4 more (zeros)
 
 struct F9Params {
@@ -1592,24 +1562,13 @@ __global__ void pack_final9x9_kernel(const float* __restrict__ w, uint4* __restr
 template <int KH, int NG, int S>
 static int launch_conv3ch(I9Params p, hipStream_t stream) {
     using C = I3Cfg<KH, NG, S>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv_c3to64_bf16_kernel<KH, NG, S>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = vcg_allow_dyn_lds((const void*)conv_c3to64_bf16_kernel<KH, NG, S>, C::LDS)) return e;
     const int nblk = p.cout / 64;
     int per = 1024 / nblk;
     if (per > p.total) per = p.total;
     conv_c3to64_bf16_kernel<KH, NG, S><<<per * nblk, NT, C::LDS, stream>>>(p);
     VCG_LAUNCH_CHECK();
     return VCG_OK;
-}
-
-static int vcg_xcd_group() {
-    // measured neutral (profiles/r03_xcd_group_ab.txt): off unless VCG_XCD_GROUP=1
-    static const int v = [] { const char* e = getenv("VCG_XCD_GROUP"); return e != nullptr && e[0] == '1' ? 1 : 0; }();
-    return v;
 }
 
 extern "C" {
@@ -1672,7 +1631,7 @@ int vcg_conv2d_bf16_stats_records(const vcg_conv_desc* d, int32_t stats_mode) {
     if (d->n <= 0 || d->h <= 0 || d->w <= 0) return VCG_E_SHAPE;
     if (stats_mode != VCG_STATS_BATCH && stats_mode != VCG_STATS_INSTANCE) return VCG_E_UNSUPPORTED;
     if (!(d->cin == 64 && d->cout == 64 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad_top == 1 && d->pad_left == 1)) return VCG_E_UNSUPPORTED;
-    if (getenv("VCG_CONV3X3_V1") != nullptr || !v2_image_fits(d->h, d->w)) return VCG_E_UNSUPPORTED;
+    if (!v2_image_fits(d->h, d->w)) return VCG_E_UNSUPPORTED;
     const long tiles_img = (long)ceil_div(d->w, V2_TC) * ceil_div(d->h, V2_TR), total = tiles_img * d->n;
     if (stats_mode == VCG_STATS_INSTANCE) return (int)(2 * tiles_img);
     return (int)(2 * (total < 256 ? total : 256));
@@ -1713,58 +1672,43 @@ int vcg_conv2d_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* w_pac
             if (!ep->stats) return VCG_E_NULL;
             if (vcg_conv2d_bf16_stats_records(d, ep->stats_mode) <= 0 || act != VCG_ACT_NONE || ep->residual) return VCG_E_UNSUPPORTED;
         }
-        static bool attr_set = false;
-        if (!attr_set) {
-            for (auto f : {(const void*)conv3x3_c64_bf16_kernel<false, false, false>, (const void*)conv3x3_c64_bf16_kernel<false, false, true>,
-                           (const void*)conv3x3_c64_bf16_kernel<false, true, false>, (const void*)conv3x3_c64_bf16_kernel<false, true, true>,
-                           (const void*)conv3x3_c64_bf16_kernel<true, false, false>, (const void*)conv3x3_c64_bf16_kernel<true, false, true>,
-                           (const void*)conv3x3_c64_bf16_kernel<true, true, false>, (const void*)conv3x3_c64_bf16_kernel<true, true, true>}) {
-                hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, WB + XB + PB);
-                if (e != hipSuccess) return (int)e;
-            }
-            attr_set = true;
-        }
         const bool aff = p.scale || p.shift, slope = act != VCG_ACT_NONE, res = p.res != nullptr;
-        // v2 (one wave per SIMD, weights in registers) unless there is a residual input or the image is too large for one
-        // buffer descriptor; VCG_CONV3X3_V1=1 forces v1 (A/B aid: scripts/gpu_v2_ab.sh)
-        static const bool use_v1 = getenv("VCG_CONV3X3_V1") != nullptr;
-        if (!use_v1 && !res && v2_image_fits(d->h, d->w)) {
-            p.tiles_x = ceil_div(d->w, V2_TC);
-            p.tiles_y = ceil_div(d->h, V2_TR);
-            p.total = p.n * p.tiles_x * p.tiles_y;
-            static bool attr2_set = false;
-            if (!attr2_set) {
-                for (auto f : {(const void*)conv3x3_c64_bf16_v2_kernel<false, false>, (const void*)conv3x3_c64_bf16_v2_kernel<false, true>,
-                               (const void*)conv3x3_c64_bf16_v2_kernel<true, false>, (const void*)conv3x3_c64_bf16_v2_kernel<true, true>,
-                               (const void*)conv3x3_c64_bf16_v2_kernel<true, false, true>}) {
-                    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, V2_LDS);
-                    if (e != hipSuccess) return (int)e;
-                }
-                attr2_set = true;
-            }
-            const int grid2 = p.total < 256 ? p.total : 256;
-#define VCG_C3V2_LAUNCH(A, S) conv3x3_c64_bf16_v2_kernel<A, S><<<grid2, V2_NT, V2_LDS, stream>>>(p)
-            if (p.stats) {
-                conv3x3_c64_bf16_v2_kernel<true, false, true><<<grid2, V2_NT, V2_LDS, stream>>>(p);      // a null scale / shift reads as 1 / 0
-            } else if (aff) {
-                if (slope) VCG_C3V2_LAUNCH(true, true); else VCG_C3V2_LAUNCH(true, false);
+        // (the launches below name the instantiations in the order the code object has always held them: v1's eight, then v2's five)
+        // v1 where there is a residual input or the image is too large for one buffer descriptor
+        if (res || !v2_image_fits(d->h, d->w)) {
+            const int grid = p.total < 256 ? p.total : 256;
+#define VCG_C3_LAUNCH(A, S, R) do {                                                                                        \
+        if (int e = vcg_allow_dyn_lds((const void*)conv3x3_c64_bf16_kernel<A, S, R>, WB + XB + PB)) return e;             \
+        conv3x3_c64_bf16_kernel<A, S, R><<<grid, NT, WB + XB + PB, stream>>>(p);                                          \
+    } while (0)
+            if (!aff) {
+                if (!slope) { if (!res) VCG_C3_LAUNCH(false, false, false); else VCG_C3_LAUNCH(false, false, true); }
+                else { if (!res) VCG_C3_LAUNCH(false, true, false); else VCG_C3_LAUNCH(false, true, true); }
             } else {
-                if (slope) VCG_C3V2_LAUNCH(false, true); else VCG_C3V2_LAUNCH(false, false);
+                if (!slope) { if (!res) VCG_C3_LAUNCH(true, false, false); else VCG_C3_LAUNCH(true, false, true); }
+                else { if (!res) VCG_C3_LAUNCH(true, true, false); else VCG_C3_LAUNCH(true, true, true); }
             }
-#undef VCG_C3V2_LAUNCH
+#undef VCG_C3_LAUNCH
             VCG_LAUNCH_CHECK();
             return VCG_OK;
         }
-        const int grid = p.total < 256 ? p.total : 256;
-#define VCG_C3_LAUNCH(A, S, R) conv3x3_c64_bf16_kernel<A, S, R><<<grid, NT, WB + XB + PB, stream>>>(p)
-        if (aff) {
-            if (slope) { if (res) VCG_C3_LAUNCH(true, true, true); else VCG_C3_LAUNCH(true, true, false); }
-            else { if (res) VCG_C3_LAUNCH(true, false, true); else VCG_C3_LAUNCH(true, false, false); }
+        // v2 (one wave per SIMD, weights in registers) everywhere else
+        p.tiles_x = ceil_div(d->w, V2_TC);
+        p.tiles_y = ceil_div(d->h, V2_TR);
+        p.total = p.n * p.tiles_x * p.tiles_y;
+        const int grid2 = p.total < 256 ? p.total : 256;
+#define VCG_C3V2_LAUNCH(...) do {                                                                                          \
+        if (int e = vcg_allow_dyn_lds((const void*)conv3x3_c64_bf16_v2_kernel<__VA_ARGS__>, V2_LDS)) return e;            \
+        conv3x3_c64_bf16_v2_kernel<__VA_ARGS__><<<grid2, V2_NT, V2_LDS, stream>>>(p);                                     \
+    } while (0)
+        if (!p.stats && !aff) {
+            if (!slope) VCG_C3V2_LAUNCH(false, false); else VCG_C3V2_LAUNCH(false, true);
+        } else if (!p.stats) {
+            if (!slope) VCG_C3V2_LAUNCH(true, false); else VCG_C3V2_LAUNCH(true, true);
         } else {
-            if (slope) { if (res) VCG_C3_LAUNCH(false, true, true); else VCG_C3_LAUNCH(false, true, false); }
-            else { if (res) VCG_C3_LAUNCH(false, false, true); else VCG_C3_LAUNCH(false, false, false); }
+            VCG_C3V2_LAUNCH(true, false, true);          // a null scale / shift reads as 1 / 0
         }
-#undef VCG_C3_LAUNCH
+#undef VCG_C3V2_LAUNCH
         VCG_LAUNCH_CHECK();
         return VCG_OK;
     }
@@ -1803,15 +1747,10 @@ int vcg_conv_transpose2d_bf16_fwd(const vcg_conv_desc* d, const void* x, const v
     p.tiles_y = ceil_div(d->h, TR);
     p.total = p.n * p.tiles_x * p.tiles_y;
     p.slope = act == VCG_ACT_LRELU ? ep->act_alpha : 1.f;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)convt3x3_c64_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WB + TXB + 256);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = vcg_allow_dyn_lds((const void*)convt3x3_c64_bf16_kernel, WB + TXB + 256)) return e;
     int per = 256 / nblk;                       // workgroups per output-channel block
     if (per > p.total) per = p.total;
-    p.xcd_group = vcg_xcd_group();
+    p.xcd_group = 0;      // always the plain mapping; dropping the parameter changes device code and waits for a change that measures
     convt3x3_c64_bf16_kernel<<<per * nblk, NT, WB + TXB + 256, stream>>>(p);
     VCG_LAUNCH_CHECK();
     return VCG_OK;
@@ -1842,7 +1781,6 @@ int vcg_conv9x9_to3_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* 
     p.h = d->h;
     p.w_ = d->w;
     p.strips = ceil_div(d->w, 64);
-    static const int max_grid = getenv("VCG_F9_GRID") ? atoi(getenv("VCG_F9_GRID")) : 512;      // tuning aid (scripts/micro/f9_stamps.py)
     // segments per column strip: the split that minimises the rows the busiest workgroup marches through -- rounds of items per
     // workgroup x (segment height + 8 recomputed halo rows).  (Round 2 halved the height until the items filled the grid twice: 25 % halo
     // rows at C3's shape, and at C4's 1080 items on 512 workgroups = a third round for 56 of them.)
@@ -1852,25 +1790,21 @@ int vcg_conv9x9_to3_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* 
         for (int segs = 1; segs <= ceil_div(d->h, 16); ++segs) {
             const int sh = ceil_div(d->h, segs);
             if (ceil_div(d->h, sh) != segs) continue;                             // (the same height reached with fewer segments)
-            const long items = (long)colstrips * segs, rounds = (items + max_grid - 1) / max_grid, cost = rounds * (sh + 8);
+            const long items = (long)colstrips * segs, rounds = (items + F9_MAX_GRID - 1) / F9_MAX_GRID, cost = rounds * (sh + 8);
             if (best < 0 || cost < best) { best = cost; p.sh = sh; p.segs = segs; }
         }
     }
     p.total = p.n * p.strips * p.segs;
     p.tanh_act = tanh_act;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv9x9_c256to3_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS);
-        if (e != hipSuccess) return (int)e;
-        e = hipFuncSetAttribute((const void*)conv9x9_c256to3_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    const int grid = p.total < max_grid ? p.total : max_grid;
+    const int grid = p.total < F9_MAX_GRID ? p.total : F9_MAX_GRID;
     // the descriptor form needs the image, four rows above and four below it inside 32-bit offsets
-    const bool buf = ((long)d->h + 8) * d->w * 512 + 65536 <= 0xFFFFFFE0l && getenv("VCG_F9_PTR") == nullptr;
-    if (buf) conv9x9_c256to3_bf16_kernel<true><<<grid, 256, F_LDS, stream>>>(p);
-    else conv9x9_c256to3_bf16_kernel<false><<<grid, 256, F_LDS, stream>>>(p);
+    const bool buf = ((long)d->h + 8) * d->w * 512 + 65536 <= 0xFFFFFFE0l;
+#define VCG_F9_LAUNCH(BUF) do {                                                                                            \
+        if (int e = vcg_allow_dyn_lds((const void*)conv9x9_c256to3_bf16_kernel<BUF>, F_LDS)) return e;                    \
+        conv9x9_c256to3_bf16_kernel<BUF><<<grid, 256, F_LDS, stream>>>(p);                                                \
+    } while (0)
+    if (buf) VCG_F9_LAUNCH(true); else VCG_F9_LAUNCH(false);
+#undef VCG_F9_LAUNCH
     VCG_LAUNCH_CHECK();
     return VCG_OK;
 }
@@ -1938,14 +1872,9 @@ static int launch_conv9x9_3ch(const vcg_conv_desc* d, int cout, const void* x, c
     p.tiles_y = ceil_div(d->h, TR);
     p.total = p.n * p.tiles_x * p.tiles_y;
     p.oh = d->h; p.ow = d->w; p.pad_top = 4; p.pad_left = 4; p.slope = 1.f;
-    p.xcd_group = vcg_xcd_group();
+    p.xcd_group = 0;      // always the plain mapping; dropping the parameter changes device code and waits for a change that measures
     using C = I3Cfg<9, 3, 1>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv_c3to64_bf16_kernel<9, 3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = vcg_allow_dyn_lds((const void*)conv_c3to64_bf16_kernel<9, 3, 1>, C::LDS)) return e;
     const int per = conv9x9_3ch_wgs(d, cout);
     conv_c3to64_bf16_kernel<9, 3, 1><<<per * nblk, NT, C::LDS, stream>>>(p);
     VCG_LAUNCH_CHECK();
@@ -1967,7 +1896,7 @@ int vcg_conv3ch_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* wfra
     p.w = (const uint4*)wfrag;
     p.bias = (const float*)bias;
     p.alpha = nullptr;
-    p.xcd_group = vcg_xcd_group();
+    p.xcd_group = 0;      // always the plain mapping; dropping the parameter changes device code and waits for a change that measures
     p.slope = lrelu_slope;
     p.y = (__bf16*)y;
     p.z = nullptr;

@@ -14,13 +14,8 @@
 // at -- but it serves every shape with one code path at several times the fp32 kernels' rate, and the data gradient of a
 // strided convolution is the same kernel run once per output phase with that phase's tap list.
 #include "vcg_common.hpp"
-#include <cstdlib>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int GC_MAXTAPS = 25;
 
@@ -49,12 +44,6 @@ struct GcParams {
     float* stats;           // LDS-tiled kernel only: per-tile sums / sums of squares of the stored output, [n][tiles per image][2][mch]
     GcTap taps[GC_MAXTAPS];
 };
-
-__device__ __forceinline__ void swap32u(float& a, float& b) {
-    const u32x2 sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    a = __uint_as_float(sw.x);
-    b = __uint_as_float(sw.y);
-}
 
 __device__ __forceinline__ bf16x8 ld_frag(vcg_rsrc r, unsigned off) {
     return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
@@ -159,7 +148,7 @@ __global__ __launch_bounds__(256, (NT == 4 ? 2 : 4)) void gconv_bf16_kernel(cons
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     float lo = acc[m][t][8 * q + j], hi = acc[m][t][8 * q + 4 + j];
-                    swap32u(lo, hi);
+                    swap32(lo, hi);
                     v[j] = lo;
                     v[4 + j] = hi;
                 }
@@ -232,12 +221,6 @@ struct GlParams {
 };
 
 struct GlSrc { int img, y0, x0, mg, ty, tx, ph; };   // a (tile, output-channel group, phase) pair: image, halo origin, group, tile coordinates, phase
-
-__device__ __forceinline__ void gl_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 // HALF: a layer with 64 output channels (the data gradient of a 64-channel layer, the transposed convolution's data gradient) would leave two
 // of the four waves without a 32-channel block; there a wave owns one of the TWO blocks x one HALF of the tile's rows instead (no statistics in this form).
@@ -321,7 +304,7 @@ __global__ __launch_bounds__(HALF ? 512 : 256, 1) void gconv_lds_bf16_kernel(con
         }
         if (AHEAD == 2) __builtin_amdgcn_s_waitcnt(WAIT_ONE_BEHIND);
         else __builtin_amdgcn_s_waitcnt(0x0F70);
-        gl_barrier();
+        lds_barrier();
         while (true) {
             request(ap, ac, abuf);
             succ(ap, ac);
@@ -330,7 +313,7 @@ __global__ __launch_bounds__(HALF ? 512 : 256, 1) void gconv_lds_bf16_kernel(con
             if (pr >= p.pairs) break;                            // the compute waves multiply their last entry without another barrier
             if (AHEAD == 2) __builtin_amdgcn_s_waitcnt(WAIT_ONE_BEHIND);
             else __builtin_amdgcn_s_waitcnt(0x0F70);
-            gl_barrier();
+            lds_barrier();
         }
         __builtin_amdgcn_s_waitcnt(0x0F70);                      // (nothing of this wave may still be writing LDS when the workgroup ends)
         return;
@@ -340,7 +323,7 @@ __global__ __launch_bounds__(HALF ? 512 : 256, 1) void gconv_lds_bf16_kernel(con
         for (int k = 0; k < NDMA; ++k) dma(cur, 0, 0, k, true);
         __builtin_amdgcn_s_waitcnt(0x0F70);
     }
-    gl_barrier();
+    lds_barrier();
 
     f32x16 acc[TRW];
 #pragma unroll
@@ -425,7 +408,7 @@ __global__ __launch_bounds__(HALF ? 512 : 256, 1) void gconv_lds_bf16_kernel(con
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         float lo = acc[n][8 * q + j], hi = acc[n][8 * q + 4 + j];
-                        swap32u(lo, hi);
+                        swap32(lo, hi);
                         v[j] = lo;
                         v[4 + j] = hi;
                     }
@@ -479,7 +462,7 @@ __global__ __launch_bounds__(HALF ? 512 : 256, 1) void gconv_lds_bf16_kernel(con
         if (last_chunk && !has_next) break;
         // the next (tile, chunk)'s pieces were issued under this chunk's MFMAs: retire them, then the one barrier of the chunk
         if (!LOADERS) __builtin_amdgcn_s_waitcnt(0x0F70);
-        gl_barrier();
+        lds_barrier();
         buf = buf + 1 == NS ? 0 : buf + 1;
         c = nc;
         if (last_chunk) { pair = npair; cur = nxt; }
@@ -538,22 +521,16 @@ __global__ void f32_to_bf16_kernel(const float* __restrict__ x, __bf16* __restri
 template <int SP, bool HALF, bool EPI = false>
 int launch_gconv_lds_sp(const GlParams& q, int grid, hipStream_t st) {
     constexpr int HR = GL_TR + SP, HC = GL_TC + SP, CH16 = HR * HC * 8, NDMA = (CH16 + 255) / 256, LDS = (HALF && 3 * NDMA * 4096 <= 160 * 1024 ? 3 : 2) * NDMA * 4096;
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)gconv_lds_bf16_kernel<SP, HALF, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return (int)e;
-        attr = true;
-    }
+    if (int e = vcg_allow_dyn_lds((const void*)gconv_lds_bf16_kernel<SP, HALF, EPI>, LDS)) return e;
     hipLaunchKernelGGL((gconv_lds_bf16_kernel<SP, HALF, EPI>), dim3(grid), dim3(HALF ? 512 : 256), LDS, st, q);
     VCG_LAUNCH_CHECK();
     return VCG_OK;
 }
 
 // the LDS-tiled kernel where it applies (input stride 1 or 2, 64-channel input chunks, >= 64 output channels, the taps of a parity plane
-// inside a 5x5 box, images below 4 GiB, enough tiles to fill the chip); VCG_GCONV_LDS=0 forces the streaming kernel (A/B aid)
+// inside a 5x5 box, images below 4 GiB, enough tiles to fill the chip)
 bool plan_gconv_lds(const GcParams& p, GlParams& q, int& spe_out, bool& half_out, int force_spe = 0, bool check_pairs = true) {
-    static const bool off = getenv("VCG_GCONV_LDS") && atoi(getenv("VCG_GCONV_LDS")) == 0;
-    if (off || p.isy != p.isx || p.isy < 1 || p.isy > 2 || p.kch % 64 || p.mblocks < 2 || p.ntaps < 1) return false;
+    if (p.isy != p.isx || p.isy < 1 || p.isy > 2 || p.kch % 64 || p.mblocks < 2 || p.ntaps < 1) return false;
     if ((long)p.ih * p.iw * p.kch * 2 > 0xFFFFFFE0l || (long)p.oh * p.ow * p.mch * 2 > 0xFFFFFFE0l) return false;
     q = GlParams{};
     // taps by the parity plane of the input they read: dy = isy * a + py
@@ -671,8 +648,7 @@ int launch_gconv(GcParams& p, hipStream_t st) {
     const long tiles = (total + 31) / 32;
     // 4 tiles per wave (128 accumulator registers, half the operand loads per MFMA) once there is enough work to fill the chip
     const int mgroups = (p.mblocks + 1) / 2;
-    static const int force_nt = getenv("VCG_GCONV_NT") ? atoi(getenv("VCG_GCONV_NT")) : 0;       // tuning aid (scripts/kbench_gconv.py)
-    const bool big = force_nt ? force_nt == 4 : tiles * mgroups >= 4096;
+    const bool big = tiles * mgroups >= 4096;
     const int nt = big ? 4 : 2;
     const long wgs = (tiles + 4 * nt - 1) / (4 * nt);
     if (wgs > 0x7fffffffL) return VCG_E_SHAPE;
@@ -871,8 +847,7 @@ int vcg_conv2d_nhwc_bf16_dgrad(const vcg_conv_desc* d, const void* dy, const voi
             }
             phases[np++] = p;
         }
-    static const bool merge_off = getenv("VCG_GCONV_MERGE_PHASES") && atoi(getenv("VCG_GCONV_MERGE_PHASES")) == 0;      // A/B aid
-    if (all && np == 4 && !merge_off) {
+    if (all && np == 4) {
         int lrc = VCG_OK;
         if (try_gconv_lds_phases(phases, np, stream, &lrc)) return lrc;
     }

@@ -17,34 +17,8 @@
 //   * every wave dumps its raw accumulators per slab; a second kernel sums the slabs in a fixed order (deterministic)
 //     into the caller's kernel layout (strides) -- Keras' (kh,kw,in,out) for Conv2D, (kh,kw,out,in) for Conv2DTranspose.
 #include "vcg_common.hpp"
-#include <utility>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-
-template <class F, int... Is>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, Is...>) {
-    (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) {
-    sfor_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-__device__ __forceinline__ void lds_barrier_g() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-__device__ __forceinline__ unsigned long long tr_read_g(unsigned addr) {
-    unsigned long long v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
 
 template <int K, int S>
 struct GwCfg {
@@ -167,26 +141,26 @@ __global__ __launch_bounds__((GwCfg<K, S>::NTH), 1) void gwgrad_bf16_kernel(GwPa
     for (; tile < p.total; tile += p.slabs, buf = buf + 1 == C::NS ? 0 : buf + 1) {
         if (C::NS == 3 && tile + p.slabs < p.total) __builtin_amdgcn_s_waitcnt(C::WAIT_ONE_BEHIND);
         else __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0): this wave's part of the stage has landed
-        lds_barrier_g();                             // ... and everyone else's; the stage multiplied last is free again
+        lds_barrier();                             // ... and everyone else's; the stage multiplied last is free again
         const int next = tile + (C::NS - 1) * p.slabs;
         if (next < p.total) dma(next, buf == 0 ? C::NS - 1 : buf - 1);
         const unsigned lb = lds0 + buf * C::BUF;
 
-        sfor<C::KSTEPS>([&](auto ic) {
+        static_for<C::KSTEPS>([&](auto ic) {
             constexpr int ks = decltype(ic)::value;          // TC = 16: one k-step per output row
             constexpr int ro = ks;
             unsigned long long fa[2][2], fb[2][2][2];
 #pragma unroll
             for (int coh = 0; coh < 2; ++coh)
 #pragma unroll
-                for (int t = 0; t < 2; ++t) fa[coh][t] = tr_read_g(lb + abase[coh] + (unsigned)((ro * C::TC + 4 * t) * 128));
+                for (int t = 0; t < 2; ++t) fa[coh][t] = tr_read(lb + abase[coh] + (unsigned)((ro * C::TC + 4 * t) * 128));
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int cih = 0; cih < 2; ++cih)
 #pragma unroll
                     for (int t = 0; t < 2; ++t)
-                        fb[i][cih][t] = tr_read_g(lb + bbase[i][cih] + (unsigned)((ro * S * C::PITCH + 4 * t) * 128));
+                        fb[i][cih][t] = tr_read(lb + bbase[i][cih] + (unsigned)((ro * S * C::PITCH + 4 * t) * 128));
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[1][0]), "+v"(fa[1][1]), "+v"(fb[0][0][0]), "+v"(fb[0][0][1]),
                            "+v"(fb[0][1][0]), "+v"(fb[0][1][1]), "+v"(fb[1][0][0]), "+v"(fb[1][0][1]), "+v"(fb[1][1][0]), "+v"(fb[1][1][1]));
@@ -325,8 +299,7 @@ template <int K, int S>
 int launch_gw(const GwParams& p, int grid, hipStream_t st) {
     using C = GwCfg<K, S>;
     auto kern = gwgrad_bf16_kernel<K, S>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::NS * C::BUF);
-    if (e != hipSuccess) return (int)e;
+    if (int e = vcg_allow_dyn_lds(reinterpret_cast<const void*>(kern), C::NS * C::BUF)) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NTH), C::NS * C::BUF, st, p);
     VCG_LAUNCH_CHECK();
     return VCG_OK;

@@ -9,11 +9,9 @@
 // sliding K x K window of pixels in registers (each input pixel is loaded once per output row, not K times).  fp32 weights and accumulation;
 // activations are the bf16 values as stored.
 #include "vcg_common.hpp"
-#include <utility>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 template <int K> constexpr int seg_len() { return 16 / K * K; }         // outputs per wave job: a multiple of K (the window's slot rotation)
 

@@ -8,7 +8,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int SPB = 512;         // pixels per block of the partial passes (4 blocks per CU at the C2 trunk shape: 2048 ran one block per CU at 1.4 TB/s)
 

@@ -16,32 +16,8 @@
 //     pixels fetched from a zero page);
 //   * per-wave partial blocks go to the workspace and are summed in a fixed order (deterministic) into Keras' layout.
 #include "vcg_common.hpp"
-#include <utility>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-template <class F, int... Is>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
-    (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-__device__ __forceinline__ unsigned long long tr_read(unsigned addr) {
-    unsigned long long v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
 
 constexpr int G_R = 8, G_C = 32;                       // output-pixel tile
 constexpr int G_DYB = G_R * G_C * 128;                 // 32768
@@ -232,7 +208,6 @@ __global__ __launch_bounds__(G_NWT * 64, 1) void wgrad3x3_c64_bf16_kernel(WgPara
                 for (int coh = 0; coh < 2; ++coh)
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
-                        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
                         const bf16x4 v4 = __builtin_bit_cast(bf16x4, fa[coh][t]);
                         dbs[coh] += ((float)v4[0] + (float)v4[1]) + ((float)v4[2] + (float)v4[3]);
                     }
@@ -241,7 +216,6 @@ __global__ __launch_bounds__(G_NWT * 64, 1) void wgrad3x3_c64_bf16_kernel(WgPara
             for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
                 for (int cih = 0; cih < 2; ++cih) {
-                    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
                     const u64x2 bv = {fb[dx][cih][0], fb[dx][cih][1]};
                     const bf16x8 b = __builtin_bit_cast(bf16x8, bv);
 #pragma unroll
@@ -367,12 +341,7 @@ int vcg_conv2d_bf16_wgrad(const vcg_conv_desc* d, const void* x, const void* dy,
     p.tiles_x = ceil_div(d->w, G_C);
     p.tiles_y = ceil_div(d->h, G_R);
     p.total = p.n * p.tiles_x * p.tiles_y;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)wgrad3x3_c64_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * G_BUF);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = vcg_allow_dyn_lds((const void*)wgrad3x3_c64_bf16_kernel, 2 * G_BUF)) return e;
     const int grid = p.total < G_GRID ? p.total : G_GRID;
     wgrad3x3_c64_bf16_kernel<<<grid, G_NWT * 64, 2 * G_BUF, stream>>>(p);
     VCG_LAUNCH_CHECK();

@@ -18,34 +18,8 @@
 //   * per-wave partial blocks go to the workspace as raw register dumps and are summed in a fixed order (deterministic); the bias gradient
 //     (sum of dz) rides along from the dz fragments.
 #include "vcg_common.hpp"
-#include <utility>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-
-template <class F, int... Is>
-__device__ __forceinline__ void w3_static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
-    (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void w3_static_for(F&& f) {
-    w3_static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-__device__ __forceinline__ void w3_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-__device__ __forceinline__ unsigned long long w3_tr_read(unsigned addr) {
-    unsigned long long v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
 
 template <int K, int S>
 struct W3Cfg {
@@ -150,12 +124,12 @@ __global__ __launch_bounds__(256, 2) void wgrad3_bf16_kernel(W3Params p) {
     auto read_a = [&](unsigned lb, int set, int ks) {
         const int i = ks >> 1, cb = ks & 1;
 #pragma unroll
-        for (int t = 0; t < 2; ++t) fa[set][t] = w3_tr_read(lb + abase + (unsigned)((i * C::TC + cb * 16 + 4 * t) * 128));
+        for (int t = 0; t < 2; ++t) fa[set][t] = tr_read(lb + abase + (unsigned)((i * C::TC + cb * 16 + 4 * t) * 128));
     };
     auto read_b = [&](unsigned lb, int set, int ks, int j) {
         const int i = ks >> 1, cb = ks & 1;
 #pragma unroll
-        for (int t = 0; t < 2; ++t) fb[set][j][t] = w3_tr_read(lb + bbase[j] + (unsigned)((S * i * C::HCA + S * (cb * 16 + 4 * t)) * 8));
+        for (int t = 0; t < 2; ++t) fb[set][j][t] = tr_read(lb + bbase[j] + (unsigned)((S * i * C::HCA + S * (cb * 16 + 4 * t)) * 8));
     };
     // s_waitcnt lgkmcnt(0) that also ties the fragment registers of a set to itself (nothing may use them before it)
     static_assert(C::NTW == 1 || C::NTW == 6, "wgrad3: the fragment sets are tied to the wait by name");
@@ -187,7 +161,7 @@ __global__ __launch_bounds__(256, 2) void wgrad3_bf16_kernel(W3Params p) {
     for (; tile < p.total; tile += nbx, buf = buf + 1 == C::NS ? 0 : buf + 1) {
         // a wave's loads retire in order: "at most NDMA outstanding" = this tile's stage is complete, the next one's may still be in flight
         __builtin_amdgcn_s_waitcnt(C::WAIT_ONE_BEHIND);
-        w3_barrier();                                // ... and everyone else's part; the stage multiplied last is free again
+        lds_barrier();                                // ... and everyone else's part; the stage multiplied last is free again
         const int next = tile + 2 * nbx;
         const bool has_next = next < p.total;
         W3Src nsrc = decode(has_next ? next : bx);
@@ -199,7 +173,7 @@ __global__ __launch_bounds__(256, 2) void wgrad3_bf16_kernel(W3Params p) {
         for (int j = 0; j < C::NTW; ++j) read_b(lb, 0, 0, j);
         W3_WAIT_SET(0);
         // k-steps of 16 output pixels: tile row ks >> 1, column half ks & 1
-        w3_static_for<C::KS>([&](auto ic) {
+        static_for<C::KS>([&](auto ic) {
             constexpr int ks = decltype(ic)::value, c = ks & 1, n = c ^ 1;
             const u64x2 av = {fa[c][0], fa[c][1]};
             const bf16x8 a = __builtin_bit_cast(bf16x8, av);
@@ -313,10 +287,7 @@ template <int K, int S>
 int launch_w3(const W3Params& p, float* dw, float* db, hipStream_t st) {
     using C = W3Cfg<K, S>;
     auto kern = wgrad3_bf16_kernel<K, S>;
-    if (C::NS * C::BUF > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::NS * C::BUF);
-        if (e != hipSuccess) return (int)e;
-    }
+    if (int e = vcg_allow_dyn_lds(reinterpret_cast<const void*>(kern), C::NS * C::BUF)) return e;
     hipLaunchKernelGGL(kern, dim3(p.grid * p.co_blocks), dim3(256), C::NS * C::BUF, st, p);
     VCG_LAUNCH_CHECK();
     const int total = p.co_blocks * 4 * C::WAVE_FLOATS + p.cout;     // raw dump elements + bias channels

@@ -16,12 +16,8 @@
 //     operand fragments of the next k-step are read behind the MFMAs of this one;
 //   * per-wave partial blocks go to the workspace as raw register dumps and are summed in a fixed order (deterministic).
 #include "vcg_common.hpp"
-#include <utility>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 
 constexpr int W9_TR = 4, W9_TC = 32, W9_NT = 11;
 constexpr int W9_NWV = 4, W9_NTH = W9_NWV * 64;                  // waves = quarters of the (11 + 1 dummy) column tiles; a wave holds ALL four row tiles
@@ -45,27 +41,6 @@ struct W9Params {
     float* ws;                   // [2 halves][grid][4 waves][W9_WAVE_FLOATS]
     int n, h, w_, tiles_x, tiles_y, total, grid;
 };
-
-template <class F, int... Is>
-__device__ __forceinline__ void w9_static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
-    (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void w9_static_for(F&& f) {
-    w9_static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-__device__ __forceinline__ void w9_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-__device__ __forceinline__ unsigned long long w9_tr_read(unsigned addr) {
-    unsigned long long v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
 
 __global__ __launch_bounds__(W9_NTH, 1) void wgrad9x9_c256to3_bf16_kernel(W9Params p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -144,12 +119,12 @@ __global__ __launch_bounds__(W9_NTH, 1) void wgrad9x9_c256to3_bf16_kernel(W9Para
     auto read_a = [&](unsigned lb, int set, int ks, int m) {
         const int i = ks >> 1, cb = ks & 1;
 #pragma unroll
-        for (int t = 0; t < 2; ++t) fa[set][m][t] = w9_tr_read(lb + abase[m] + (unsigned)((i * W9_TC + cb * 16 + 4 * t) * 256));
+        for (int t = 0; t < 2; ++t) fa[set][m][t] = tr_read(lb + abase[m] + (unsigned)((i * W9_TC + cb * 16 + 4 * t) * 256));
     };
     auto read_b = [&](unsigned lb, int set, int ks, int j) {
         const int i = ks >> 1, cb = ks & 1;
 #pragma unroll
-        for (int t = 0; t < 2; ++t) fb[set][j][t] = w9_tr_read(lb + bbase[j] + (unsigned)((i * W9_DC + cb * 16 + 4 * t) * 8));
+        for (int t = 0; t < 2; ++t) fb[set][j][t] = tr_read(lb + bbase[j] + (unsigned)((i * W9_DC + cb * 16 + 4 * t) * 8));
     };
 #define W9_WAIT_SET(S_)                                                                                                                       \
     asm volatile("s_waitcnt lgkmcnt(0)"                                                                                                       \
@@ -172,7 +147,7 @@ __global__ __launch_bounds__(W9_NTH, 1) void wgrad9x9_c256to3_bf16_kernel(W9Para
         // a wave's loads retire in order: "at most NDMA outstanding" = this tile's stage is complete, the next one's may still be in flight
         if (tile + nbx < p.total) __builtin_amdgcn_s_waitcnt(W9_WAIT_ONE_BEHIND);
         else __builtin_amdgcn_s_waitcnt(0x0F70);
-        w9_barrier();                                // ... and everyone else's part; the stage multiplied last is free again
+        lds_barrier();                                // ... and everyone else's part; the stage multiplied last is free again
         const int next = tile + 2 * nbx;
         const bool has_next = next < p.total;
         const Src nsrc = decode(has_next ? next : tile);
@@ -184,7 +159,7 @@ __global__ __launch_bounds__(W9_NTH, 1) void wgrad9x9_c256to3_bf16_kernel(W9Para
         for (int j = 0; j < W9_NTW; ++j) read_b(lb, 0, 0, j);
         W9_WAIT_SET(0);
         // k-steps of 16 pixels: tile row ks >> 1, column half ks & 1
-        w9_static_for<W9_KS>([&](auto ic) {
+        static_for<W9_KS>([&](auto ic) {
             constexpr int ks = decltype(ic)::value, c = ks & 1, n = c ^ 1;
 #pragma unroll
             for (int j = 0; j < W9_NTW; ++j) {
@@ -261,7 +236,6 @@ __global__ void pack_dz3_bf16_kernel(const float* __restrict__ dz, __bf16* __res
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n * hw) return;
     const long img = i / hw, px = i - img * hw;
-    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
     bf16x4 v;
     v[0] = (__bf16)dz[(img * 3 + 0) * hw + px];
     v[1] = (__bf16)dz[(img * 3 + 1) * hw + px];
@@ -299,12 +273,7 @@ int vcg_conv9x9_to3_bf16_wgrad(const vcg_conv_desc* d, const void* x, const floa
     const long px = (long)d->n * d->h * d->w;
     pack_dz3_bf16_kernel<<<(unsigned)((px + 255) / 256), 256, 0, stream>>>(dz, (__bf16*)dzb, d->n, (long)d->h * d->w);
     VCG_LAUNCH_CHECK();
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)wgrad9x9_c256to3_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, W9_NS * W9_BUF);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = vcg_allow_dyn_lds((const void*)wgrad9x9_c256to3_bf16_kernel, W9_NS * W9_BUF)) return e;
     wgrad9x9_c256to3_bf16_kernel<<<dim3(2 * p.grid), W9_NTH, W9_NS * W9_BUF, stream>>>(p);
     VCG_LAUNCH_CHECK();
     static_assert(W9_WAVE_FLOATS % 64 == 0, "wgrad9 reduce: 64 raw elements per block stay inside one wave block");

@@ -589,11 +589,7 @@ int launch_cout1(ConvParams p, hipStream_t st) {
 
 template <typename Kern>
 int launch_with_lds(Kern kern, int grid, size_t lds, const ConvParams& p, hipStream_t st) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
+    if (int e = vcg_allow_dyn_lds(reinterpret_cast<const void*>(kern), lds)) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, p);
     VCG_LAUNCH_CHECK();
     return VCG_OK;

@@ -16,31 +16,8 @@
 //     no VGPRs), double buffered; B operands are conflict-free ds_read_b32 at compile-time offsets;
 //   * work item = (image, 64-column strip, segment of output rows); one workgroup per CU, 2 waves per SIMD.
 #include "vcg_common.hpp"
-#include <utility>
 
 namespace {
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void swap32(float& a, float& b) {      // lanes 32-63 of a <-> lanes 0-31 of b
-    const u32x2 sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    a = __uint_as_float(sw.x);
-    b = __uint_as_float(sw.y);
-}
-
-template <class F, int... Is>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
-    (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 constexpr int R_NW = 8;                      // waves = input-channel slices
 constexpr int R_CI = 32;                     // channels per wave
@@ -223,12 +200,7 @@ int vcg_internal_conv9_rowchain(const float* x, const float* w, float* y, int n,
     p.total = n * p.strips * p.segs;
     p.ws_t = ws_t; p.ws_m = ws_m; p.ws_k = ws_k;
     p.act = act;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv9x9_rowchain_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, R_LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = vcg_allow_dyn_lds((const void*)conv9x9_rowchain_f32_kernel, R_LDS)) return e;
     const int grid = p.total < 256 ? p.total : 256;
     conv9x9_rowchain_f32_kernel<<<grid, R_NW * 64, R_LDS, st>>>(p);
     VCG_LAUNCH_CHECK();

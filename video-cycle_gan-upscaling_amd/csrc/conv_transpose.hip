@@ -246,11 +246,7 @@ int launch_convt(ConvTParams p, hipStream_t st) {
     const long grid = (long)p.tiles_x * p.tiles_y * p.co_blocks * p.n;
     if (grid <= 0 || grid > 0x7fffffffL) return VCG_E_SHAPE;
     auto kern = convt_kernel<K, CBY, CBX, CK, MT>;
-    if (C::LDS_BYTES > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-    }
+    if (int e = vcg_allow_dyn_lds(reinterpret_cast<const void*>(kern), C::LDS_BYTES)) return e;
     hipLaunchKernelGGL(kern, dim3((int)grid), dim3(256), C::LDS_BYTES, st, p);
     VCG_LAUNCH_CHECK();
     return VCG_OK;

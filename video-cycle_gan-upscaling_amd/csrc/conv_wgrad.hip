@@ -348,11 +348,7 @@ int launch_wgrad(const WgradParams& p, int grid, hipStream_t st) {
     using C = WgCfg<S, NW, NJ, MW, TH, KH, KW>;
     static_assert(C::LDS_BYTES <= 160 * 1024, "wgrad tile does not fit the 160 KiB LDS");
     auto kern = wgrad_kernel<S, NW, NJ, MW, TH, KH, KW>;
-    if (C::LDS_BYTES > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-    }
+    if (int e = vcg_allow_dyn_lds(reinterpret_cast<const void*>(kern), C::LDS_BYTES)) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), C::LDS_BYTES, st, p);
     VCG_LAUNCH_CHECK();
     return VCG_OK;

@@ -16,14 +16,6 @@ import torch
 
 from . import _lib as L
 
-import os
-
-# VCG_FUSED_STATS=0: the normalisations' statistics by their own pass over the tensor instead of the producing convolution's epilogue (A/B aid)
-FUSED_STATS = os.environ.get("VCG_FUSED_STATS", "1") != "0"
-# VCG_FOLD_PREDICT=0: learning-phase-0 passes of the bf16 trunk as conv -> separate normalisation pass (A/B aid)
-FOLD_PREDICT = os.environ.get("VCG_FOLD_PREDICT", "1") != "0"
-STATS_EPILOGUE_F32 = os.environ.get("VCG_STATS_EPILOGUE_F32", "1") != "0"      # fp32 path: normalisation statistics from the convolutions' epilogues (A/B aid)
-
 BN_EPS = 1e-3          # keras BatchNormalization defaults
 BN_MOMENTUM = 0.99
 IN_EPS = 1e-5          # instance norm (canonical CycleGAN value; no reference counterpart)
@@ -267,7 +259,7 @@ class Conv2D(Layer):
         rt = self.rt
         n, _, h, w = x.shape
         d = self.desc(n, h, w)
-        nrec = rt.lib.vcg_conv2d_stats_records(ctypes.byref(d), L.STATS_INSTANCE if instance else L.STATS_BATCH) if STATS_EPILOGUE_F32 else -1
+        nrec = rt.lib.vcg_conv2d_stats_records(ctypes.byref(d), L.STATS_INSTANCE if instance else L.STATS_BATCH)
         if nrec <= 0 or self.act != L.ACT_NONE:
             y, ctx = self.forward(x, tag=tag)
             return y, ctx, None
@@ -728,7 +720,7 @@ class Conv3x3Bf16(Layer):
         n, h, wd, _ = x.shape
         mode = L.STATS_INSTANCE if instance else L.STATS_BATCH
         d = L.ConvDesc(n, 64, h, wd, 64, h, wd, 3, 3, 1, 1, 1)
-        nrec = rt.lib.vcg_conv2d_bf16_stats_records(ctypes.byref(d), mode) if FUSED_STATS else -1
+        nrec = rt.lib.vcg_conv2d_bf16_stats_records(ctypes.byref(d), mode)
         if nrec <= 0:
             y, ctx = self.forward(x, tag)
             return y, ctx, None
@@ -846,7 +838,7 @@ class Conv2DBf16(Conv2D):
         n, h, w, _ = x.shape
         d = self.desc(n, h, w)
         mode = L.STATS_INSTANCE if instance else L.STATS_BATCH
-        nrec = rt.lib.vcg_conv2d_nhwc_bf16_stats_records(ctypes.byref(d), mode) if FUSED_STATS else -1
+        nrec = rt.lib.vcg_conv2d_nhwc_bf16_stats_records(ctypes.byref(d), mode)
         if nrec <= 0:
             y, ctx = self.forward(x, tag=tag)
             return y, ctx, None
@@ -1089,23 +1081,6 @@ def f32_to_bf16(rt, x):
     return y
 
 
-TAIL_CHUNK_MB = int(os.environ.get("VCG_TAIL_CHUNK_MB", "0"))       # 0 (default): whole-batch launches of the up-sampling block and final/conv
-
-
-def tail_chunk(n, h, w, cout=256):
-    """frames per launch of the up-sampling block and final/conv (h, w: the block's INPUT size) -- an experiment kept behind
-    VCG_TAIL_CHUNK_MB, OFF by default.  The tensor between the two layers (model.py:288-291) is 2 cout bytes per output pixel -- 134 MB per
-    512x512 frame -- and only final/conv reads it in the forward pass: walked one chunk of at most TAIL_CHUNK_MB at a time, final/conv could
-    find its input in the 256 MiB Infinity Cache.  Measured (profiles/r03_tail_chunk_ab.txt): it does not pay -- per-frame launches of the
-    two kernels take 59 + 60 us against 47 + 42 us per frame in the whole-batch launches (too few tiles per launch to fill 256 CUs evenly),
-    C5 4563 against 5149 frames/s, C3's shard 522 against 533."""
-    per = 4 * h * w * cout * 2
-    budget = TAIL_CHUNK_MB << 20
-    if TAIL_CHUNK_MB <= 0 or per > budget:
-        return n
-    return max(1, min(n, budget // per))
-
-
 class ConvT3x3Bf16(ConvT2D):
     """upsampling_block (model.py:70-75) with bf16 activations: Conv2DTranspose(3, strides 2) 64 -> 64m + bias + LeakyReLU forward on
     vcg_conv_transpose2d_bf16_fwd (bf16 NHWC in and out).  Backward takes the gradient dz in front of the activation (the bf16 data
@@ -1137,12 +1112,11 @@ class ConvT3x3Bf16(ConvT2D):
             self._pvalid = True
         return self._wp, self._wg
 
-    def forward(self, x, tag=None, out=None):
-        """out: optional preallocated [n, 2h, 2w, cout] bf16 tensor (a slice of a whole-batch tensor when the caller walks the batch in chunks)"""
+    def forward(self, x, tag=None):
         rt = self.rt
         n, h, w, _ = x.shape
         wp, _ = self._packed()
-        y = out if out is not None else torch.empty(n, 2 * h, 2 * w, self.cout, dtype=torch.bfloat16, device=rt.device)
+        y = torch.empty(n, 2 * h, 2 * w, self.cout, dtype=torch.bfloat16, device=rt.device)
         d = self.desc(n, h, w)
         ep = L.EpilogueBf16(None, self.ps[self.name + "/bias"].data_ptr(), self.act, float(self.alpha), None, None)
         with Timed(rt, tag):
@@ -1215,12 +1189,12 @@ class FinalConv9x9Bf16(Conv2D):
             self._pvalid = True
         return self._wf, self._wd
 
-    def forward(self, x, residual=None, tag=None, out=None):
+    def forward(self, x, residual=None, tag=None):
         rt = self.rt
         n, h, w, _ = x.shape
         wf, _ = self._packed()
         d = self.desc(n, h, w)
-        y = out if out is not None else rt.empty(n, 3, h, w)
+        y = rt.empty(n, 3, h, w)
         with Timed(rt, tag):
             L.check(rt.lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
                                                     1 if self.act == L.ACT_TANH else 0, y.data_ptr(), rt.stream), "vcg_conv9x9_to3_bf16_fwd")

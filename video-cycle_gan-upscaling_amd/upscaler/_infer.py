@@ -136,12 +136,11 @@ class Bf16Generator:
         """frames per launch of the up-sampling stages and final/conv.  Beyond the k3 x2 topology, a launch's largest tensor (the
         last stage's output, 2 * 256 bytes per pixel) stays below 4 GiB: the kernels' offsets are 32-bit inside an image, and final/conv's
         descriptor covers the whole launch"""
-        ch = E.tail_chunk(n, h, w)
         if self.legacy:
-            return ch
+            return n
         f = 2 ** len(self.ups)
         per = f * f * h * w * 256 * 2
-        ch = max(1, min(ch, 0xFFFFFFE0 // per))
+        ch = max(1, min(n, 0xFFFFFFE0 // per))
         launches = -(-n // ch)
         return -(-n // launches)                 # the same number of launches, frames spread evenly (32 -> 16 + 16, not 31 + 1)
 

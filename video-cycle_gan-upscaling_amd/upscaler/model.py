@@ -13,7 +13,6 @@ Extensions named by north_star with no reference counterpart (SURVEY.md section 
   make_discriminator_patchgan_70, ``norm='instance'``.
 """
 import math
-import os
 from abc import ABCMeta, abstractmethod
 from collections import OrderedDict
 
@@ -399,12 +398,6 @@ class VGG19Features(Model):
         return d
 
 
-# A/B switches of the bench scripts ("0" = the fp32 layers on layout-converted copies that the bf16 edge layers replaced)
-INIT_BF16 = os.environ.get("VCG_INIT_BF16", "1") != "0"      # generator: initial/conv + PReLU straight into bf16 NHWC
-HEAD_BF16 = os.environ.get("VCG_HEAD_BF16", "1") != "0"      # PatchGAN: the one-channel last convolution on bf16 NHWC
-FIRST_BF16 = os.environ.get("VCG_FIRST_BF16", "1") != "0"    # critics: block 1 (3 input channels) straight into bf16 NHWC
-
-
 class UpscalerOrig(Model):
     """make_upscaler_orig topology (model.py:267-295)."""
 
@@ -431,7 +424,7 @@ class UpscalerOrig(Model):
         k = kernel_size
         nrm = {"batch": "batch", "instance": "instance"}[norm]
         # 'bf16+tail': initial/conv + PReLU write the bf16 NHWC trunk input directly (one launch; E.InitialConv9x9Bf16)
-        self.init_bf16 = bool(self.tail_bf16 and output_image_shape[2] == 3 and INIT_BF16)
+        self.init_bf16 = bool(self.tail_bf16 and output_image_shape[2] == 3)
         self.c_init = self._add((E.InitialConv9x9Bf16 if self.init_bf16 else E.Conv2D)("initial/conv", output_image_shape[2], filters, 9))
         self.a_init = self._add(E.NormAct("initial/prelu_op", filters, None, L.ACT_PRELU, prelu_name="initial/prelu"))
         self.blocks = []
@@ -476,14 +469,14 @@ class UpscalerOrig(Model):
         skip = h
         bf = self.trunk_dtype == "bf16"
         folds = {}
-        if bf and not training and self.n_pre.norm == "batch" and E.FOLD_PREDICT and len(self.blocks) * 2 + 1 <= 48:
+        if bf and not training and self.n_pre.norm == "batch" and len(self.blocks) * 2 + 1 <= 48:
             # every folded BatchNormalization of the pass in one launch
             folds = E.fold_batch(self.rt, [p for b in self.blocks for p in ((b[0], b[1]), (b[2], b[3]))] + [(self.c_pre, self.n_pre)])
 
         def conv_norm(cv, nm, h, residual=None):
             """conv -> norm[-> act][+ residual]; on the bf16 trunk the convolution's epilogue hands the norm its statistics, and in
             learning phase 0 (predict) the whole group is one launch (BatchNormalization folded into the epilogue)"""
-            if bf and not training and nm.norm == "batch" and E.FOLD_PREDICT:
+            if bf and not training and nm.norm == "batch":
                 tape.extend((None, None))
                 return cv.forward_folded(h, nm, residual=residual, tag="trunk_conv", folded=folds.get(id(cv)))
             if nm.needs_stats(training):          # (both dtypes: the convolution's epilogue hands the norm its statistics)
@@ -501,27 +494,6 @@ class UpscalerOrig(Model):
         h = conv_norm(self.c_pre, self.n_pre, h, residual=skip)
         if self.trunk_dtype == "bf16" and not self.tail_bf16:
             h = E.from_bf16_nhwc(self.rt, h)
-        if self.tail_bf16 and len(self.ups) == 1:
-            # up-sampling block -> final/conv in chunks of frames small enough for the Infinity Cache (E.tail_chunk): final/conv reads the
-            # 256-channel tensor right after it was written.  Training keeps the whole tensor for the backward pass (each chunk is a slice of
-            # it); predict re-uses one chunk buffer.
-            n, hh, ww, _ = h.shape
-            ch = E.tail_chunk(n, hh, ww, self.ups[0].cout)
-            if ch < n:
-                up = self.ups[0]
-                y = self.rt.empty(n, 3, 2 * hh, 2 * ww)
-                uall = torch.empty(n, 2 * hh, 2 * ww, up.cout, dtype=torch.bfloat16, device=self.rt.device) if training else None
-                for i in range(0, n, ch):
-                    c = min(ch, n - i)
-                    u, _ = up.forward(h[i:i + c], tag="convt", out=uall[i:i + c] if training else None)
-                    self.c_fin.forward(u, tag="final_conv", out=y[i:i + c])
-                    del u
-                if training:
-                    tape.append((h, uall, up.desc(n, hh, ww)))
-                    tape.append((uall, y, self.c_fin.desc(n, 2 * hh, 2 * ww)))
-                else:
-                    tape.extend((None, None))
-                return y, tape
         for u in self.ups:
             h, a = u.forward(h, tag="convt"); tape.append(a)
         h, a = self.c_fin.forward(h, tag="final_conv"); tape.append(a)
@@ -594,7 +566,7 @@ class DiscriminatorStack(Model):
         for i, f in enumerate(filters):
             n = "discriminator/block_%d" % (i + 1)
             s = strides[i]
-            first_bf = dtype == "bf16" and i == 0 and FIRST_BF16 and cin == 3 and f % 64 == 0 and (kernel, s) == (3, 1)
+            first_bf = dtype == "bf16" and i == 0 and cin == 3 and f % 64 == 0 and (kernel, s) == (3, 1)
             bf = dtype == "bf16" and (i > 0 or first_bf)
             conv = E.FirstConvBf16 if first_bf else E.Conv2DBf16 if bf else E.Conv2D
             norm = E.NormActBf16 if bf else E.NormAct
@@ -702,10 +674,10 @@ class DiscriminatorPatchGAN(Model):
                 bf = dtype == "bf16"
                 cv = self._add((E.Conv2DBf16 if bf else E.Conv2D)(n + "/Conv2d", cin, f, 4, s, 1))
                 na = self._add((E.NormActBf16 if bf else E.NormAct)(n + "/BatchNorm", f, norm, L.ACT_LRELU, 0.2))
-            elif i == 0 and dtype == "bf16" and FIRST_BF16 and cin == 3:
+            elif i == 0 and dtype == "bf16" and cin == 3:
                 cv = self._add(E.FirstConvBf16(n + "/Conv2d", cin, f, 4, s, 1, L.ACT_LRELU, 0.2))   # fp32 NCHW frames -> bf16 NHWC in one launch
                 na = None
-            elif last and dtype == "bf16" and HEAD_BF16:
+            elif last and dtype == "bf16":
                 cv = self._add(E.ConvCout1Bf16(n + "/Conv2d", cin, f, 4, s, 1))         # reads / writes the bf16 NHWC tensor directly
                 na = None
             else:
