@@ -429,6 +429,8 @@ int vcg_conv9x9_to3_bf16_wgrad(const vcg_conv_desc* d, const void* x, const floa
  * Weights as MFMA operand fragments: vcg_pack_conv_frag_bf16(w, taps, mdim, kdim, mode, out), out = taps*mdim*kdim bf16:
  *   mode 0: w is a Keras (kh,kw,in,out) kernel, packed for the forward pass       (mdim = out, kdim = in)
  *   mode 1: the same kernel packed for its data gradient                           (mdim = in,  kdim = out)
+ *   mode 2: mode 1 with the taps reversed: the data gradient of a stride-1 'same' layer run as a forward convolution over dy
+ *           (vcg_conv2d_bf16_fwd 5x5 with the residual epilogue: a gradient joining at the layer's input is added before the rounding)
  * (a Conv2DTranspose kernel (kh,kw,out,in) is a Conv2D kernel with the roles of in / out exchanged.) */
 size_t vcg_conv_frag_bf16_bytes(int taps, int mdim, int kdim);
 int vcg_pack_conv_frag_bf16(const float* w, int taps, int mdim, int kdim, int mode, void* out, hipStream_t stream);
@@ -456,16 +458,23 @@ int vcg_conv_transpose2d_nhwc_bf16_fwd(const vcg_conv_desc* d, const void* x, co
  * OUTPUT mask_src is and which feeds the layer. */
 int vcg_conv2d_nhwc_bf16_dgrad(const vcg_conv_desc* d, const void* dy, const void* wfrag_t, const void* mask_src, float mask_slope,
                                void* dx, hipStream_t stream);
-/* weight / bias gradient, x [n][h][w][cin] and dy [n][oh][ow][cout] bf16 NHWC, 3x3 / 4x4, stride 1 / 2, channels multiples of 64;
- * dw fp32 in Keras' (kh,kw,in,out) layout, dbias fp32 [cout] or NULL (deterministic: fixed-order sum of per-workgroup partials) */
+/* weight / bias gradient, x [n][h][w][cin] and dy [n][oh][ow][cout] bf16 NHWC, 3x3 / 4x4 / 5x5, stride 1 / 2, channels multiples of 64;
+ * dw fp32 in Keras' (kh,kw,in,out) layout, dbias fp32 [cout] or NULL (deterministic: fixed-order sum of per-workgroup partials).
+ * 5x5 (the trunk of kernel_size=5 generators, model.py:267): the 25 taps are split over two workgroups per (ci, co) block pair, so the
+ * workspace holds 14 instead of 13 wave dumps per pair and slab.  Other kernel sizes / strides / channel counts: the query returns 0
+ * and the call VCG_E_UNSUPPORTED. */
 size_t vcg_conv2d_nhwc_bf16_wgrad_workspace_bytes(const vcg_conv_desc* d);
 int vcg_conv2d_nhwc_bf16_wgrad(const vcg_conv_desc* d, const void* x, const void* dy, float* dw_hwio, float* dbias, void* ws, size_t ws_bytes,
                                hipStream_t stream);
 /* Conv2DTranspose(strides=2,'same') (upscaling/upscaler/model.py:72): weight gradient from the layer input x [n][h][w][cin] and the
- * gradient dz [n][oh][ow][cout] in front of its activation, both bf16 NHWC; dw fp32 in Keras' (kh,kw,out,in) layout */
+ * gradient dz [n][oh][ow][cout] in front of its activation, both bf16 NHWC; dw fp32 in Keras' (kh,kw,out,in) layout.  3x3 / 4x4 / 5x5,
+ * cin and cout multiples of 64 (64 -> 256 and 256 -> 256: both up-sampling stages of an x4 generator) */
 size_t vcg_conv_transpose2d_nhwc_bf16_wgrad_workspace_bytes(const vcg_conv_desc* d);
 int vcg_conv_transpose2d_nhwc_bf16_wgrad(const vcg_conv_desc* d, const void* x, const void* dz, float* dw_hwoi, void* ws, size_t ws_bytes,
                                          hipStream_t stream);
+/* dx = y_act > 0 ? dy : bf16(dy * slope), flat over count bf16 elements (16-byte aligned pointers; dx may alias dy): the gradient in
+ * front of a LeakyReLU from the one behind it and the activation's OUTPUT y_act -- between two up-sampling stages of an x4 generator */
+int vcg_lrelu_bwd_bf16(const void* dy, const void* y_act, float slope, void* dx, size_t count, hipStream_t stream);
 /* flat precision changes (Flatten of an NHWC tensor IS its memory order: the Dense head of the discriminators stays fp32) */
 int vcg_bf16_to_f32(const void* x, float* y, size_t count, hipStream_t stream);
 int vcg_f32_to_bf16(const float* x, void* y, size_t count, hipStream_t stream);

@@ -472,6 +472,7 @@ __global__ __launch_bounds__(HALF ? 512 : 256, 1) void gconv_lds_bf16_kernel(con
 // out[((wt*ksteps + ks)*mblocks + mb)*64 + lane][j] = W(m = mb*32 + (lane&31), k = ks*16 + 8*(lane>>5) + j, tap wt)
 //   mode 0: W(m, k, t) = w[(t*kdim + k)*mdim + m]     a Keras (kh,kw,in,out) kernel read as conv forward  (m = out, k = in)
 //   mode 1: W(m, k, t) = w[(t*mdim + m)*kdim + k]     the same kernel read for its data gradient          (m = in,  k = out)
+//   mode 2: mode 1 with the taps in reverse order: the data gradient of a stride-1 'same' layer as a FORWARD convolution over dy
 __global__ void pack_frag_kernel(const float* __restrict__ w, __bf16* __restrict__ out, int taps, int mdim, int kdim, int mode) {
     const int ksteps = kdim >> 4, mblocks = mdim >> 5;
     const long total = (long)taps * ksteps * mblocks * 64 * 8;
@@ -482,7 +483,8 @@ __global__ void pack_frag_kernel(const float* __restrict__ w, __bf16* __restrict
         const int ks = (int)(q % ksteps);
         const int t = (int)(q / ksteps);
         const int m = mb * 32 + (lane & 31), k = ks * 16 + 8 * (lane >> 5) + j;
-        const float v = mode == 0 ? w[((long)t * kdim + k) * mdim + m] : w[((long)t * mdim + m) * kdim + k];
+        const int ts = mode == 2 ? taps - 1 - t : t;
+        const float v = mode == 0 ? w[((long)t * kdim + k) * mdim + m] : w[((long)ts * mdim + m) * kdim + k];
         out[idx] = (__bf16)v;
     }
 }
@@ -516,6 +518,22 @@ __global__ void bf16_to_f32_kernel(const __bf16* __restrict__ x, float* __restri
 __global__ void f32_to_bf16_kernel(const float* __restrict__ x, __bf16* __restrict__ y, size_t count) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < count) y[i] = (__bf16)x[i];
+}
+
+// dx = m > 0 ? dy : dy * slope: the derivative of the LeakyReLU whose OUTPUT m is, between two up-sampling stages of an x4 generator's
+// backward (bf16 in and out, one rounding; dx may alias dy); 8 elements per thread, the tail (count % 8) by the first threads
+__global__ void lrelu_bwd_bf16_kernel(const __bf16* dy, const __bf16* __restrict__ m, __bf16* dx, size_t count, float slope) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, v8 = count / 8;
+    auto f = [&](__bf16 g, __bf16 mv) { return (float)mv > 0.f ? g : (__bf16)((float)g * slope); };
+    if (i < v8) {
+        const bf16x8 gv = ((const bf16x8*)dy)[i], mv = ((const bf16x8*)m)[i];
+        bf16x8 r;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) r[e] = f(gv[e], mv[e]);
+        ((bf16x8*)dx)[i] = r;
+    }
+    const size_t t = v8 * 8 + i;
+    if (i < 8 && t < count) dx[t] = f(dy[t], m[t]);
 }
 
 template <int SP, bool HALF, bool EPI = false>
@@ -681,7 +699,7 @@ size_t vcg_conv_frag_bf16_bytes(int taps, int mdim, int kdim) { return (size_t)t
 
 int vcg_pack_conv_frag_bf16(const float* w, int taps, int mdim, int kdim, int mode, void* out, hipStream_t stream) {
     VCG_CHECK_PTR(w); VCG_CHECK_PTR(out);
-    if (taps <= 0 || mdim <= 0 || kdim <= 0 || mdim % 32 || kdim % 16 || (mode != 0 && mode != 1)) return VCG_E_UNSUPPORTED;
+    if (taps <= 0 || mdim <= 0 || kdim <= 0 || mdim % 32 || kdim % 16 || mode < 0 || mode > 2) return VCG_E_UNSUPPORTED;
     const long total = (long)taps * mdim * kdim;
     hipLaunchKernelGGL(pack_frag_kernel, dim3((unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256)), dim3(256), 0, stream, w,
                        (__bf16*)out, taps, mdim, kdim, mode);
@@ -711,6 +729,16 @@ int vcg_f32_to_bf16(const float* x, void* y, size_t count, hipStream_t stream) {
     VCG_CHECK_PTR(x); VCG_CHECK_PTR(y);
     if (count == 0) return VCG_OK;
     hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, x, (__bf16*)y, count);
+    VCG_LAUNCH_CHECK();
+    return VCG_OK;
+}
+
+int vcg_lrelu_bwd_bf16(const void* dy, const void* y_act, float slope, void* dx, size_t count, hipStream_t stream) {
+    VCG_CHECK_PTR(dy); VCG_CHECK_PTR(y_act); VCG_CHECK_PTR(dx);
+    if (count == 0) return VCG_OK;
+    if ((((size_t)dy | (size_t)y_act | (size_t)dx) & 15) || count / 8 + 8 > 0x7fffffffull * 256) return VCG_E_UNSUPPORTED;
+    hipLaunchKernelGGL(lrelu_bwd_bf16_kernel, dim3((unsigned)((count / 8 + 8 + 255) / 256)), dim3(256), 0, stream, (const __bf16*)dy,
+                       (const __bf16*)y_act, (__bf16*)dx, count, slope);
     VCG_LAUNCH_CHECK();
     return VCG_OK;
 }

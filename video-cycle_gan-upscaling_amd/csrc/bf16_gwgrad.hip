@@ -1,6 +1,6 @@
 // Generic bf16 NHWC weight gradient on v_mfma_f32_32x32x16_bf16: the weight / bias gradients of the discriminators'
 // Conv2D layers in the bf16 configs (upscaling/upscaler/model.py:839-871, 904-936; PatchGAN) and of the generator's
-// Conv2DTranspose (model.py:72), 3x3 / 4x4 kernels, stride 1 or 2, channel counts that are multiples of 64:
+// Conv2DTranspose (model.py:72), 3x3 / 4x4 / 5x5 kernels, stride 1 or 2, channel counts that are multiples of 64:
 //     dW[tap][ci][co] = sum over (n, oy, ox) of  x[n][oy*S + ky - pt][ox*S + kx - pl][ci] * dy[n][oy][ox][co]      (fp32)
 // The contraction runs over PIXELS while NHWC keeps channels contiguous: both MFMA operands are needed transposed (8
 // consecutive pixels of one channel per lane).  As in the trunk's kernel (bf16_wgrad.hip) they come from the natural
@@ -8,6 +8,10 @@
 // addressed by lanes (i>>2)+4j: one read = 4 pixels x 16 channels, two reads = one operand fragment).
 //   * workgroup = one (64 output channels) x (64 input channels) block of dW, ALL taps: wave w keeps taps 2w, 2w+1 (two
 //     [64 co] x [64 ci] blocks = 128 accumulator registers) for the whole launch; ceil(K*K/2) waves (5 / 8);
+//   * 5x5: 25 taps would be 13 waves of 128 registers each, less than the accumulators alone.  The taps are split over a
+//     TAP-GROUP grid index instead: group 0 holds taps 0..13 (ky 0..2), group 1 taps 14..24 (ky 2..4), 7 waves per workgroup
+//     (two per SIMD, as the 4x4 form).  A group stages only the halo rows its three ky rows touch ((TR-1)*S + 3 instead
+//     of + 5) and dy once more -- the price of the split; the reduction sees the groups as 14 waves of one workgroup;
 //   * persistent over pixel tiles (S = 1: 8 x 16 output pixels, S = 2: 4 x 16); a tile's dy pixels and x halo stream
 //     HBM/L2 -> LDS by buffer_load ... lds through a ring of three stages (two where three do not fit), out-of-image pixels zero-filled by the descriptor's range check;
 //   * LDS image: 128-byte pixel rows (this block's 64 channels); the two 64-byte halves of a row are swapped when bit 1 of
@@ -23,11 +27,16 @@ namespace {
 template <int K, int S>
 struct GwCfg {
     static constexpr int T = K * K;
-    static constexpr int NW = (T + 1) / 2;                      // waves: two taps each
+    static constexpr int G = K == 5 ? 2 : 1;                    // tap groups (a grid index): 5x5 does not fit one workgroup's registers
+    static constexpr int TPG = G == 1 ? T : 14;                 // taps per group (the last group holds the rest)
+    static constexpr int KSPAN = G == 1 ? K : 3;                // kernel rows a group touches, from row (g * TPG) / K on
+    static_assert(G * TPG >= T && (G == 1 || TPG % 2 == 0), "the groups cover all taps; a wave's two taps belong to one group");
+    static_assert(G == 1 || ((TPG - 1) / K + 1 == KSPAN && (T - 1) / K - TPG / K + 1 == KSPAN), "rows touched by the two groups");
+    static constexpr int NW = (TPG + 1) / 2;                    // waves per workgroup: two taps each
     static constexpr int NTH = NW * 64;
     static constexpr int TR = S == 1 ? 8 : 4, TC = 16;          // output-pixel tile
     static constexpr int KSTEPS = TR * TC / 16;
-    static constexpr int XR = (TR - 1) * S + K;                 // halo rows
+    static constexpr int XR = (TR - 1) * S + KSPAN;             // halo rows (of this tap group)
     static constexpr int XC = (TC - 1) * S + K;                 // halo columns (image space)
     static constexpr int HALF = (XC + 1) / 2;                   // stride 2: number of even columns
     static constexpr int XPOS = S == 2 ? 2 * HALF : XC;         // stored column positions
@@ -48,7 +57,7 @@ struct GwCfg {
 struct GwParams {
     const unsigned char* x;      // bf16 NHWC [n][h][w][cin]
     const unsigned char* dy;     // bf16 NHWC [n][oh][ow][cout]
-    float* ws;                   // [slab][pair][wave][WAVE_FLOATS]
+    float* ws;                   // [slab][pair][tap group][wave][WAVE_FLOATS]
     float* wsb;                  // [slab][co block][2 lane halves][64]
     int n, h, w_, cin, oh, ow, cout, pt, pl;
     int tiles_x, tiles_y, total, slabs, ci_blocks, co_blocks;
@@ -62,6 +71,8 @@ __global__ __launch_bounds__((GwCfg<K, S>::NTH), 1) void gwgrad_bf16_kernel(GwPa
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned lds0 = (unsigned)(size_t)smem;
     int b = blockIdx.x;
+    const int grp = b % C::G; b /= C::G;                                      // tap group: taps grp*TPG .., kernel rows ky0 ..
+    const int ky0 = grp * C::TPG / K;
     const int cib = b % p.ci_blocks; b /= p.ci_blocks;
     const int cob = b % p.co_blocks; b /= p.co_blocks;
     const int slab = b;
@@ -72,12 +83,13 @@ __global__ __launch_bounds__((GwCfg<K, S>::NTH), 1) void gwgrad_bf16_kernel(GwPa
     unsigned abase[2];                                                        // dy: [co half]
 #pragma unroll
     for (int coh = 0; coh < 2; ++coh) abase[coh] = (unsigned)((h8 + q) * 128 + ((64 * coh + chb) ^ (64 * ((q >> 1) & 1))));
-    // x: [tap of this wave][ci half]; tap t = 2*wv + i -> (ky, kx); stored position of image column c: S == 1 ? c : de-interleaved
-    const bool tap1 = 2 * wv + 1 < C::T;
+    // x: [tap of this wave][ci half]; tap t = grp*TPG + 2*wv + i -> (ky, kx); stored position of image column c: S == 1 ? c : de-interleaved
+    const int t0 = grp * C::TPG + 2 * wv;
+    const bool tap0 = t0 < C::T, tap1 = t0 + 1 < C::T;                       // wave-uniform (several groups: TPG is even, a wave's taps stay inside its group)
     unsigned bbase[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        const int t = min(2 * wv + i, C::T - 1), ky = t / K, kx = t % K;
+        const int t = min(t0 + i, C::T - 1), ky = t / K - ky0, kx = t % K;
         const int pp0 = S == 2 ? (kx & 1) * C::HALF + (kx >> 1) : kx;         // position of the tile's first pixel for this tap
         const int sw = ((pp0 + q) >> 1) & 1;                                  // (+ multiples of 4 do not change bit 1)
 #pragma unroll
@@ -109,7 +121,7 @@ __global__ __launch_bounds__((GwCfg<K, S>::NTH), 1) void gwgrad_bf16_kernel(GwPa
     auto dma = [&](int tile, int buf) {
         const int txi = tile % p.tiles_x, t2 = tile / p.tiles_x, tyi = t2 % p.tiles_y, img = t2 / p.tiles_y;
         const int oy0 = tyi * C::TR, ox0 = txi * C::TC;
-        const int gy0 = oy0 * S - p.pt, gx0 = ox0 * S - p.pl;
+        const int gy0 = oy0 * S - p.pt + ky0, gx0 = ox0 * S - p.pl;
         const vcg_rsrc rdy = make_rsrc(p.dy + img * dyimg, (unsigned long)dyimg), rx = make_rsrc(p.x + img * ximg, (unsigned long)ximg);
         // byte offsets of the tile's first pixels (the x one may be "negative": it is only used modulo 2^32 under a passed range check)
         const unsigned dybase = (unsigned)(oy0 * p.ow + ox0) * (unsigned)dypix + (unsigned)(cob * 128);
@@ -164,7 +176,7 @@ __global__ __launch_bounds__((GwCfg<K, S>::NTH), 1) void gwgrad_bf16_kernel(GwPa
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[1][0]), "+v"(fa[1][1]), "+v"(fb[0][0][0]), "+v"(fb[0][0][1]),
                            "+v"(fb[0][1][0]), "+v"(fb[0][1][1]), "+v"(fb[1][0][0]), "+v"(fb[1][0][1]), "+v"(fb[1][1][0]), "+v"(fb[1][1][1]));
-            if (wv == 0 && cib == 0) {               // wave- and block-uniform: one wave per co block sums dy for the bias gradient
+            if (wv == 0 && cib == 0 && grp == 0) {   // wave- and block-uniform: one wave per co block sums dy for the bias gradient
 #pragma unroll
                 for (int coh = 0; coh < 2; ++coh)
 #pragma unroll
@@ -175,7 +187,7 @@ __global__ __launch_bounds__((GwCfg<K, S>::NTH), 1) void gwgrad_bf16_kernel(GwPa
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                if (i == 1 && !tap1) continue;       // wave-uniform (odd number of taps: the last wave holds one)
+                if (!(i == 0 ? tap0 : tap1)) continue;   // wave-uniform (odd number of taps: the last wave holds one; 5x5 group 1: one / none)
 #pragma unroll
                 for (int cih = 0; cih < 2; ++cih) {
                     const u64x2 bv = {fb[i][cih][0], fb[i][cih][1]};
@@ -191,7 +203,7 @@ __global__ __launch_bounds__((GwCfg<K, S>::NTH), 1) void gwgrad_bf16_kernel(GwPa
     }
 
     // raw register dump per wave (coalesced); decoded by the reduction
-    float* out = p.ws + (((long)slab * p.co_blocks * p.ci_blocks + (long)cob * p.ci_blocks + cib) * C::NW + wv) * C::WAVE_FLOATS;
+    float* out = p.ws + ((((long)slab * p.co_blocks * p.ci_blocks + (long)cob * p.ci_blocks + cib) * C::G + grp) * C::NW + wv) * C::WAVE_FLOATS;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -200,7 +212,7 @@ __global__ __launch_bounds__((GwCfg<K, S>::NTH), 1) void gwgrad_bf16_kernel(GwPa
             for (int coh = 0; coh < 2; ++coh)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) out[(((i * 2 + cih) * 2 + coh) * 16 + e) * 64 + lane] = acc[i][cih][coh][e];
-    if (wv == 0 && cib == 0 && p.wsb) {              // bias partials: [slab][co block][lane half][64 channels]
+    if (wv == 0 && cib == 0 && grp == 0 && p.wsb) {              // bias partials: [slab][co block][lane half][64 channels]
         float* bo = p.wsb + (((long)slab * p.co_blocks + cob) * 2 + (lane >> 5)) * 64;
         bo[lane & 31] = dbs[0];
         bo[32 + (lane & 31)] = dbs[1];
@@ -212,7 +224,7 @@ struct GwReduce {
     const float* wsb;
     float* dw;
     float* db;
-    int slabs, ci_blocks, co_blocks, nw, T, cin, cout;
+    int slabs, ci_blocks, co_blocks, nw, nwg, tpg, T, cin, cout;      // nw: waves of all tap groups, nwg: per group, tpg: taps per group
     long s_t, s_ci, s_co;        // dw[t*s_t + ci*s_ci + co*s_co]
 };
 
@@ -238,7 +250,7 @@ __global__ void gwgrad_reduce_kernel(GwReduce p) {
     const int cib = (int)(r % p.ci_blocks);
     const int cob = (int)(r / p.ci_blocks);
     const int l = off & 63, e = (off >> 6) & 15, tile = off >> 10, coh = tile & 1, cih = (tile >> 1) & 1, i = tile >> 2;
-    const int t = 2 * wv + i;
+    const int t = (wv / p.nwg) * p.tpg + 2 * (wv % p.nwg) + i;
     if (t >= p.T) return;
     const int co = cob * 64 + 32 * coh + (e & 3) + 8 * (e >> 2) + 4 * (l >> 5), ci = cib * 64 + 32 * cih + (l & 31);
     p.dw[(long)t * p.s_t + (long)ci * p.s_ci + (long)co * p.s_co] = (s0 + s1) + (s2 + s3);
@@ -268,24 +280,28 @@ __global__ void gwgrad_bias_reduce_kernel(GwReduce p) {
     p.db[co] = s;
 }
 
-constexpr int GW_MAX_WG = 256;       // one 5- or 8-wave workgroup per CU (the ring of stages fills its LDS), ONE round: a second round would pay the
+constexpr int GW_MAX_WG = 256;       // one 5-, 7- or 8-wave workgroup per CU (the ring of stages fills its LDS), ONE round: a second round would pay the
                                      // pipeline ramp and the accumulator dump again and double the partial blocks the reduction reads
 
-struct GwPlan { int tiles_x, tiles_y, total, slabs, ci_blocks, co_blocks, nw, TR; size_t ws_part, ws_bytes; bool ok; };
+struct GwPlan { int tiles_x, tiles_y, total, slabs, ci_blocks, co_blocks, groups, nwg, tpg, nw, TR; size_t ws_part, ws_bytes; bool ok; };
 
 GwPlan gw_plan(int n, int cin, int oh, int ow, int cout, int k, int s) {
     GwPlan pl{};
     pl.ok = false;
-    if (cin % 64 || cout % 64 || k < 3 || k > 4 || (s != 1 && s != 2)) return pl;   // 5x5: 13 waves leave 128 registers each -- fp32 path
+    if (n < 1 || oh < 1 || ow < 1 || cin < 64 || cout < 64) return pl;
+    if (cin % 64 || cout % 64 || k < 3 || k > 5 || (s != 1 && s != 2)) return pl;
     pl.TR = s == 1 ? 8 : 4;
-    pl.nw = (k * k + 1) / 2;
+    pl.groups = k == 5 ? 2 : 1;                      // GwCfg::G / TPG / NW (5x5: two tap groups of 14 / 11 taps, 7 waves each)
+    pl.tpg = k == 5 ? 14 : k * k;
+    pl.nwg = (pl.tpg + 1) / 2;
+    pl.nw = pl.groups * pl.nwg;
     pl.tiles_x = ceil_div(ow, 16);
     pl.tiles_y = ceil_div(oh, pl.TR);
     pl.total = pl.tiles_x * pl.tiles_y * n;
     pl.ci_blocks = cin / 64;
     pl.co_blocks = cout / 64;
     const int pairs = pl.ci_blocks * pl.co_blocks;
-    int slabs = GW_MAX_WG / pairs;
+    int slabs = GW_MAX_WG / (pairs * pl.groups);
     if (slabs < 1) slabs = 1;
     if (slabs > pl.total) slabs = pl.total;
     pl.slabs = slabs;
@@ -318,15 +334,15 @@ int gw_run(const void* x, const void* dy, float* dw, float* db, int n, int h, in
     p.n = n; p.h = h; p.w_ = w; p.cin = cin; p.oh = oh; p.ow = ow; p.cout = cout; p.pt = pt; p.pl = pl_;
     p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.total = pl.total; p.slabs = pl.slabs;
     p.ci_blocks = pl.ci_blocks; p.co_blocks = pl.co_blocks;
-    const int grid = pl.slabs * pl.ci_blocks * pl.co_blocks;
+    const int grid = pl.slabs * pl.ci_blocks * pl.co_blocks * pl.groups;
     int rc = VCG_E_UNSUPPORTED;
 #define VCG_GW(K_, S_) if (k == K_ && s == S_) rc = launch_gw<K_, S_>(p, grid, st)
-    VCG_GW(3, 1); VCG_GW(3, 2); VCG_GW(4, 1); VCG_GW(4, 2);
+    VCG_GW(3, 1); VCG_GW(3, 2); VCG_GW(4, 1); VCG_GW(4, 2); VCG_GW(5, 1); VCG_GW(5, 2);
 #undef VCG_GW
     if (rc != VCG_OK) return rc;
     GwReduce r{};
     r.ws = p.ws; r.wsb = p.wsb; r.dw = dw; r.db = db;
-    r.slabs = pl.slabs; r.ci_blocks = pl.ci_blocks; r.co_blocks = pl.co_blocks; r.nw = pl.nw; r.T = k * k; r.cin = cin; r.cout = cout;
+    r.slabs = pl.slabs; r.ci_blocks = pl.ci_blocks; r.co_blocks = pl.co_blocks; r.nw = pl.nw; r.nwg = pl.nwg; r.tpg = pl.tpg; r.T = k * k; r.cin = cin; r.cout = cout;
     r.s_t = s_t; r.s_ci = s_ci; r.s_co = s_co;
     const long per_slab = (long)pl.co_blocks * pl.ci_blocks * pl.nw * 8192;
     hipLaunchKernelGGL(gwgrad_reduce_kernel, dim3((unsigned)((per_slab + 255) / 256)), dim3(256), 0, st, r);

@@ -873,6 +873,109 @@ class Conv2DBf16(Conv2D):
         return dx
 
 
+class Conv5x5Bf16(Conv2D):
+    """Conv2D(64, 5, 'same') on bf16 NHWC, 64 -> 64: the trunk convolution of the reference's default generator (kernel_size=5,
+    model.py:267) with the interface UpscalerOrig uses on Conv3x3Bf16.  Training forward on vcg_conv2d_nhwc_bf16_fwd[_stats] (the
+    statistics partials of the normalisation behind it out of the epilogue), learning phase 0 on vcg_conv2d_bf16_fwd's 5x5 form with the
+    folded BatchNormalization / PReLU / Add epilogue (the launch _infer.py makes).  The data gradient is that same entry point on the
+    kernel packed tap-reversed and transposed (vcg_pack_conv_frag_bf16 mode 2); a gradient joining at the layer's input (dx_residual) is its
+    residual operand, added in fp32 before the one rounding to bf16.  Weight / bias gradient on vcg_conv2d_nhwc_bf16_wgrad (5x5: two
+    tap groups per block pair)."""
+
+    def __init__(self, name, cin=64, cout=64):
+        if cin != 64 or cout != 64:
+            raise NotImplementedError("the bf16 5x5 trunk convolution is instantiated for 64 -> 64 channels")
+        super().__init__(name, cin, cout, 5)
+        self._wf = self._wd = None
+        self._pvalid = False
+
+    def refresh(self):
+        super().refresh()
+        self._pvalid = False
+
+    def _packed(self):
+        rt = self.rt
+        if self._wf is None:
+            self._wf = torch.empty(25 * 64 * 64, dtype=torch.bfloat16, device=rt.device)
+            self._wd = torch.empty(25 * 64 * 64, dtype=torch.bfloat16, device=rt.device)
+        if not self._pvalid:
+            w = self.ps[self.name + "/kernel"].data_ptr()
+            L.check(rt.lib.vcg_pack_conv_frag_bf16(w, 25, 64, 64, 0, self._wf.data_ptr(), rt.stream), "pack fwd")
+            L.check(rt.lib.vcg_pack_conv_frag_bf16(w, 25, 64, 64, 2, self._wd.data_ptr(), rt.stream), "pack dgrad")
+            self._pvalid = True
+        return self._wf, self._wd
+
+    def forward(self, x, tag=None):
+        rt = self.rt
+        n, h, w, _ = x.shape
+        d = self.desc(n, h, w)
+        wf, _ = self._packed()
+        y = torch.empty(n, h, w, 64, dtype=torch.bfloat16, device=rt.device)
+        with Timed(rt, tag):
+            L.check(rt.lib.vcg_conv2d_nhwc_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
+                                                    L.ACT_NONE, 0.0, y.data_ptr(), rt.stream), "vcg_conv2d_nhwc_bf16_fwd[%s]" % self.name)
+        return y, (x, d)
+
+    def forward_folded(self, x, norm, residual=None, tag=None, folded=None):
+        """learning phase 0: conv + BatchNormalization (moving statistics) [+ PReLU] [+ Add] in one launch (see Conv3x3Bf16.forward_folded)"""
+        rt, ps = self.rt, self.ps
+        n, h, w, _ = x.shape
+        if folded is not None:
+            scale, shift = folded
+        else:
+            scale, shift = rt.empty(64), rt.empty(64)
+            L.check(rt.lib.vcg_bn_fold(ps[self.name + "/bias"].data_ptr(), ps[norm.name + "/moving_mean"].data_ptr(),
+                                       ps[norm.name + "/moving_variance"].data_ptr(), ps[norm.name + "/gamma"].data_ptr(),
+                                       ps[norm.name + "/beta"].data_ptr(), 64, BN_EPS, scale.data_ptr(), shift.data_ptr(), rt.stream), "vcg_bn_fold")
+        wf, _ = self._packed()
+        y = torch.empty(n, h, w, 64, dtype=torch.bfloat16, device=rt.device)
+        d = self.desc(n, h, w)
+        ep = L.EpilogueBf16(scale.data_ptr(), shift.data_ptr(), norm.act, float(norm.alpha), norm._alpha_ptr(), _ptr(residual), None, L.STATS_NONE)
+        with Timed(rt, tag and residual is not None and tag + "_res" or tag):
+            L.check(rt.lib.vcg_conv2d_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), y.data_ptr(), ctypes.byref(ep), rt.stream),
+                    "vcg_conv2d_bf16_fwd[%s]" % self.name)
+        return y
+
+    def forward_stats(self, x, instance, tag=None):
+        """forward + per-tile statistics partials of the output (see Conv3x3Bf16.forward_stats); None where the tiled kernel does not
+        serve the shape (the caller then runs the separate statistics pass)"""
+        rt = self.rt
+        n, h, w, _ = x.shape
+        d = self.desc(n, h, w)
+        nrec = rt.lib.vcg_conv2d_nhwc_bf16_stats_records(ctypes.byref(d), L.STATS_INSTANCE if instance else L.STATS_BATCH)
+        if nrec <= 0:
+            y, ctx = self.forward(x, tag)
+            return y, ctx, None
+        wf, _ = self._packed()
+        y = torch.empty(n, h, w, 64, dtype=torch.bfloat16, device=rt.device)
+        buf = rt.empty((n if instance else 1) * nrec * 2 * 64)
+        with Timed(rt, tag):
+            L.check(rt.lib.vcg_conv2d_nhwc_bf16_fwd_stats(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
+                                                          y.data_ptr(), buf.data_ptr(), rt.stream), "vcg_conv2d_nhwc_bf16_fwd_stats[%s]" % self.name)
+        return y, (x, d), (buf, nrec)
+
+    def backward(self, ctx, dy, need_dx=True, param_grads=True, which=0, dx_residual=None, tag=None):
+        """dx_residual: a gradient that joins at this layer's input (the block's skip branch), added in the epilogue"""
+        rt = self.rt
+        x, d = ctx
+        if param_grads:
+            ws, wsn = rt.workspace(rt.lib.vcg_conv2d_nhwc_bf16_wgrad_workspace_bytes(ctypes.byref(d)))
+            with Timed(rt, tag and tag + "_wgrad"):
+                L.check(rt.lib.vcg_conv2d_nhwc_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dy.data_ptr(),
+                                                          self.ps.grad(self.name + "/kernel", which).data_ptr(),
+                                                          self.ps.grad(self.name + "/bias", which).data_ptr(), ws, wsn, rt.stream),
+                        "vcg_conv2d_nhwc_bf16_wgrad[%s]" % self.name)
+        if not need_dx:
+            return None
+        _, wd = self._packed()
+        dx = torch.empty_like(x)
+        ep = L.EpilogueBf16(None, None, L.ACT_NONE, 0.0, None, _ptr(dx_residual), None, L.STATS_NONE)
+        with Timed(rt, tag and tag + ("_dgrad_res" if dx_residual is not None else "_dgrad")):
+            L.check(rt.lib.vcg_conv2d_bf16_fwd(ctypes.byref(d), dy.data_ptr(), wd.data_ptr(), dx.data_ptr(), ctypes.byref(ep), rt.stream),
+                    "vcg_conv2d_bf16_fwd[%s dgrad]" % self.name)
+        return dx
+
+
 class InitialConv9x9Bf16(Conv2D):
     """initial/conv + initial/prelu (model.py:275-276) as the entry into the bf16 layout: Conv2D(64, 9, 'same') + bias + PReLU from the
     fp32 NCHW frames to bf16 NHWC in one launch (vcg_conv9x9_from3_bf16_fwd[_train]: bf16 copies of frames and kernel as MFMA operands,
@@ -1157,6 +1260,90 @@ class ConvT3x3Bf16(ConvT2D):
         with Timed(rt, tag and tag + "_dgrad"):
             L.check(lib.vcg_conv2d_nhwc_bf16_fwd(ctypes.byref(dd), dz.data_ptr(), wg.data_ptr(), None, L.ACT_NONE, 0.0, dx.data_ptr(), rt.stream),
                     "vcg_conv2d_nhwc_bf16_fwd[%s dgrad]" % self.name)
+        return dx
+
+
+class ConvTBf16(ConvT2D):
+    """upsampling_block (model.py:70-75) on bf16 NHWC beyond the k3 x2 topology: Conv2DTranspose(k, strides 2) + bias + LeakyReLU for k in
+    {3, 5}, 64 or 256 input channels (the first and the later stages of an x4 generator), out-channels a multiple of 64.  Forward on
+    vcg_conv_transpose2d_nhwc_bf16_fwd.  Backward takes the gradient dz in front of the layer's own activation; weight gradient on
+    vcg_conv_transpose2d_nhwc_bf16_wgrad, bias gradient = per-channel sum of dz, data gradient = the stride-2 convolution over dz
+    (vcg_conv2d_nhwc_bf16_fwd), as ConvT3x3Bf16 does them."""
+
+    def __init__(self, name, cin, cout, k, act=L.ACT_NONE, alpha=0.0):
+        if k not in (3, 5) or cin not in (64, 256) or cout % 64 or cout <= 0 or act not in (L.ACT_NONE, L.ACT_LRELU):
+            raise NotImplementedError("the generic bf16 transposed convolution serves 3x3 / 5x5, 64 or 256 -> 64m channels, no activation or LeakyReLU")
+        super().__init__(name, cin, cout, k, act, alpha)
+        self._wp = self._wg = None
+        self._pvalid = False
+
+    def refresh(self):
+        super().refresh()
+        self._pvalid = False
+
+    def _packed(self):
+        rt = self.rt
+        t = self.k * self.k
+        if self._wp is None:
+            self._wp = torch.empty(t * self.cout * self.cin, dtype=torch.bfloat16, device=rt.device)
+            self._wg = torch.empty(t * self.cout * self.cin, dtype=torch.bfloat16, device=rt.device)
+        if not self._pvalid:
+            w = self.ps[self.name + "/kernel"].data_ptr()
+            # Keras' (kh,kw,out,in) kernel is the Conv2D kernel (kh,kw,in'=out,out'=in) of the stride-2 convolution dz -> dx: the forward
+            # is that convolution's data gradient (mode 1), the layer's data gradient its forward (mode 0)
+            L.check(rt.lib.vcg_pack_conv_frag_bf16(w, t, self.cout, self.cin, 1, self._wp.data_ptr(), rt.stream), "pack convT")
+            L.check(rt.lib.vcg_pack_conv_frag_bf16(w, t, self.cin, self.cout, 0, self._wg.data_ptr(), rt.stream), "pack convT dgrad")
+            self._pvalid = True
+        return self._wp, self._wg
+
+    def forward(self, x, tag=None):
+        rt = self.rt
+        n, h, w, _ = x.shape
+        wp, _ = self._packed()
+        y = torch.empty(n, 2 * h, 2 * w, self.cout, dtype=torch.bfloat16, device=rt.device)
+        d = self.desc(n, h, w)
+        with Timed(rt, tag):
+            L.check(rt.lib.vcg_conv_transpose2d_nhwc_bf16_fwd(ctypes.byref(d), x.data_ptr(), wp.data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
+                                                              self.act, float(self.alpha), y.data_ptr(), rt.stream),
+                    "vcg_conv_transpose2d_nhwc_bf16_fwd[%s]" % self.name)
+        return y, (x, y, d)
+
+    def backward(self, ctx, dz, need_dx=True, param_grads=True, which=0, tag=None, dz_channel_sums=None, input_lrelu_slope=None):
+        """dz: bf16 NHWC gradient in front of the LeakyReLU.  Returns dx as bf16 NHWC.  dz_channel_sums: (records, count) left by the kernel
+        that produced dz (FinalConv9x9Bf16.backward).  input_lrelu_slope: the layer's input is the OUTPUT of a LeakyReLU with this slope
+        (the up-sampling stage below); dx is then multiplied by its derivative (vcg_lrelu_bwd_bf16), i.e. it is that stage's dz."""
+        rt, lib = self.rt, self.rt.lib
+        x, _, d = ctx
+        _, wg = self._packed()
+        if param_grads:
+            ws, wsn = rt.workspace(lib.vcg_conv_transpose2d_nhwc_bf16_wgrad_workspace_bytes(ctypes.byref(d)))
+            with Timed(rt, tag and tag + "_wgrad"):
+                L.check(lib.vcg_conv_transpose2d_nhwc_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dz.data_ptr(),
+                                                                 self.ps.grad(self.name + "/kernel", which).data_ptr(), ws, wsn, rt.stream),
+                        "vcg_conv_transpose2d_nhwc_bf16_wgrad[%s]" % self.name)
+            gb = self.ps.grad(self.name + "/bias", which)
+            if dz_channel_sums is not None:
+                rec, nrec = dz_channel_sums
+                L.check(lib.vcg_sum_records(rec.data_ptr(), nrec, self.cout, 1.0, gb.data_ptr(), rt.stream), "vcg_sum_records[%s]" % self.name)
+            else:
+                # sum of dz over (n, h, w) = its per-channel mean x count (the shifted sums of vcg_norm_stats_bf16)
+                hw = d.oh * d.ow
+                mean, var = rt.empty(self.cout), rt.empty(self.cout)
+                ws, wsn = rt.workspace(lib.vcg_norm_stats_bf16_workspace_bytes(d.n, self.cout, hw, L.NORM_BATCH))
+                L.check(lib.vcg_norm_stats_bf16(dz.data_ptr(), d.n, self.cout, hw, L.NORM_BATCH, mean.data_ptr(), var.data_ptr(), ws, wsn, rt.stream),
+                        "vcg_norm_stats_bf16[%s]" % self.name)
+                axpby(rt, mean, gb, float(d.n * hw), 0.0)
+        if not need_dx:
+            return None
+        # dx[ci][i] = sum dz[co][2i + k - crop] W[k][co][ci]: a stride-2 convolution over dz (pad = the crop)
+        dd = L.ConvDesc(d.n, self.cout, d.oh, d.ow, self.cin, d.h, d.w, self.k, self.k, 2, d.pad_top, d.pad_left)
+        dx = torch.empty_like(x)
+        with Timed(rt, tag and tag + "_dgrad"):
+            L.check(lib.vcg_conv2d_nhwc_bf16_fwd(ctypes.byref(dd), dz.data_ptr(), wg.data_ptr(), None, L.ACT_NONE, 0.0, dx.data_ptr(), rt.stream),
+                    "vcg_conv2d_nhwc_bf16_fwd[%s dgrad]" % self.name)
+            if input_lrelu_slope is not None:
+                L.check(lib.vcg_lrelu_bwd_bf16(dx.data_ptr(), x.data_ptr(), float(input_lrelu_slope), dx.data_ptr(), dx.numel(), rt.stream),
+                        "vcg_lrelu_bwd_bf16[%s]" % self.name)
         return dx
 
 

@@ -159,6 +159,7 @@ SIGNATURES = {
     "vcg_conv2d_nhwc_bf16_wgrad": (c_int, [_D, _P, _P, _P, _P, _P, c_size_t, _P]),
     "vcg_conv_transpose2d_nhwc_bf16_wgrad_workspace_bytes": (c_size_t, [_D]),
     "vcg_conv_transpose2d_nhwc_bf16_wgrad": (c_int, [_D, _P, _P, _P, _P, c_size_t, _P]),
+    "vcg_lrelu_bwd_bf16": (c_int, [_P, _P, c_float, _P, c_size_t, _P]),
     "vcg_bf16_to_f32": (c_int, [_P, _P, c_size_t, _P]),
     "vcg_f32_to_bf16": (c_int, [_P, _P, c_size_t, _P]),
 }

@@ -406,18 +406,18 @@ class UpscalerOrig(Model):
         super().__init__("upscaler_orig", (output_image_shape[0] // f, output_image_shape[1] // f, output_image_shape[2]), seed)
         if trunk_dtype not in ("fp32", "bf16", "bf16+tail"):
             raise ValueError(trunk_dtype)
-        # 'bf16+tail': also the up-sampling block and final/conv on bf16 activations (forward entirely, backward where the
-        # bf16 gradient kernels exist: _engine.ConvT3x3Bf16 / FinalConv9x9Bf16); needs the x2 topology with 64 -> 256 -> 3
+        # 'bf16+tail': also the up-sampling blocks and final/conv on bf16 activations, forward and backward (64 -> 256 [-> 256 ...] -> 3)
         self.tail_bf16 = trunk_dtype == "bf16+tail"
         if self.tail_bf16:
             trunk_dtype = "bf16"
-            if upscale_factor != 2:
-                raise NotImplementedError("the bf16 tail is instantiated for upscale_factor=2")
-        if trunk_dtype == "bf16" and (kernel_size != 3 or filters != 64):
-            raise NotImplementedError("the bf16 trunk is instantiated for kernel_size=3, filters=64")
+            if upscale_factor < 2 or upscale_factor & (upscale_factor - 1):
+                raise NotImplementedError("the bf16 tail is instantiated for power-of-two upscale_factor >= 2")
+        if trunk_dtype == "bf16" and (kernel_size not in (3, 5) or filters != 64):
+            raise NotImplementedError("the bf16 trunk is instantiated for kernel_size 3 or 5, filters=64")
         self.trunk_dtype = trunk_dtype
         bf = trunk_dtype == "bf16"
-        conv = (lambda n, ci, co, kk: E.Conv3x3Bf16(n, ci, co)) if bf else (lambda n, ci, co, kk: E.Conv2D(n, ci, co, kk))
+        trunk_conv = E.Conv3x3Bf16 if kernel_size == 3 else E.Conv5x5Bf16
+        conv = (lambda n, ci, co, kk: trunk_conv(n, ci, co)) if bf else (lambda n, ci, co, kk: E.Conv2D(n, ci, co, kk))
         normact = E.NormActBf16 if bf else E.NormAct
         self.upscale_times = int(math.log(f, 2))
         self.factor = 2 ** self.upscale_times
@@ -440,13 +440,14 @@ class UpscalerOrig(Model):
         self.n_pre = self._add(normact("prefinal/batch_norm", 64, nrm))
         self.ups = []
         cin = 64
-        upc = E.ConvT3x3Bf16 if self.tail_bf16 else E.ConvT2D
+        # the k3 x2 topology keeps ConvT3x3Bf16 (its own 3x3 64 -> 64m forward kernel); 5x5 and the 256-channel stages of x4 run on the generic one
+        upc = (E.ConvT3x3Bf16 if k == 3 and self.upscale_times == 1 else E.ConvTBf16) if self.tail_bf16 else E.ConvT2D
         for i in range(self.upscale_times):
             self.ups.append(self._add(upc("upscaling/%d/block/conv_transp" % i, cin, 256, k, L.ACT_LRELU, 0.2)))
             cin = 256                                                                 # 256: model.py:288
         self.c_fin = self._add(E.FinalConv9x9Bf16("final/conv", cin, 3, 9) if self.tail_bf16 else E.Conv2D("final/conv", cin, 3, 9, act=L.ACT_TANH))
         self._finish()
-        if bf and len(self.blocks) * 2 + 1 <= 48:
+        if bf and k == 3 and len(self.blocks) * 2 + 1 <= 48:
             E.PackGroup3x3([c for b in self.blocks for c in (b[0], b[2])] + [self.c_pre])
 
     def _out_shape(self, s):
@@ -508,7 +509,11 @@ class UpscalerOrig(Model):
             # on the bf16 kernels and hand back bf16 NHWC, which is what the trunk's backward consumes
             d, sums = self.c_fin.backward(tape.pop(), dy, True, True, which, tag="final_conv", input_lrelu_slope=self.ups[-1].alpha,
                                           want_channel_sums=True)
-            d = self.ups[-1].backward(tape.pop(), d, True, True, which, tag="convt", dz_channel_sums=sums)
+            for i in range(len(self.ups) - 1, -1, -1):
+                # x4 and beyond: a stage hands the one below the gradient in front of ITS LeakyReLU (ConvTBf16); the channel sums belong to the last
+                kw = {"input_lrelu_slope": self.ups[i - 1].alpha} if i else {}
+                d = self.ups[i].backward(tape.pop(), d, True, True, which, tag="convt", dz_channel_sums=sums, **kw)
+                sums = None
         else:
             d = self.c_fin.backward(tape.pop(), dy, True, True, which, tag="final_conv")
             for u in reversed(self.ups):
