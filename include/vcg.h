@@ -325,6 +325,13 @@ int vcg_conv_transpose2d_bf16_fwd(const vcg_conv_desc* d, const void* x, const v
 int vcg_pack_final9x9_bf16(const void* w, void* out, hipStream_t stream);
 int vcg_conv9x9_to3_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* wfrag, const void* bias, int32_t tanh_act, void* y,
                              hipStream_t stream);
+/* the same layer on 128 or 256 input channels: d->cin = 128 is final/conv of make_upscaler_attention (upscaling/upscaler/model.py:326, after
+ * up-sampling blocks of 128 filters).  vcg_conv9x9_to3_bf16_fwd accepts both; wfrag is then vcg_conv9x9_to3_bf16_wfrag_bytes(cin) bytes
+ * (cin/64 * 2304 fragments of 16 bytes + 64 zero bytes; 0 for an unsupported cin) made by vcg_pack_conv9x9_to3_bf16 from Keras' (9,9,cin,3)
+ * fp32 kernel.  At cin = 256 size and contents equal VCG_FINAL9X9_WFRAG_BYTES / vcg_pack_final9x9_bf16.  The gradients of this layer
+ * (vcg_conv9x9_to3_bf16_dgrad*) stay 256-only. */
+size_t vcg_conv9x9_to3_bf16_wfrag_bytes(int32_t cin);
+int vcg_pack_conv9x9_to3_bf16(const void* w, int32_t cin, void* out, hipStream_t stream);
 
 /* initial/conv of the generator (upscaling/upscaler/model.py:275-276): Conv2D(64, 9, 'same') + bias + PReLU from the
  * fp32 NCHW frames to bf16 NHWC -- the entry into the bf16 layout.  wfrag: VCG_FIRST9X9_WFRAG_BYTES bytes of MFMA operand
@@ -356,6 +363,26 @@ int vcg_conv9x9_from3_bf16_fwd(const vcg_conv_desc* d, const void* x, const void
 size_t vcg_conv3ch_bf16_wfrag_bytes(int32_t kh, int32_t kw, int32_t cout);
 int vcg_pack_conv3ch_bf16(const void* w, int32_t kh, int32_t kw, int32_t cout, void* out, hipStream_t stream);
 int vcg_conv3ch_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* wfrag, const void* bias, float lrelu_slope, void* y, hipStream_t stream);
+
+/* Input-driven sigmoid gate of make_upscaler_attention, one launch: y = bf16(sigmoid(Conv2D(cout, k, 'same')(u) + bias) * m), replacing
+ * Conv2D + Activation('sigmoid') + Multiply of residual_block_attention (upscaling/upscaler/model.py:33-36; u = the frames, cin 3) and of
+ * upsampling_block_attention (model.py:80-90; u = Concatenate[nearest, bilinear resize of the frames], cin 6).  u: fp32 NCHW [n][cin][h][w];
+ * m, y: bf16 NHWC [n][h][w][cout]; the attention tensor is never stored, m is read once and y written once; the product is formed in fp32 and
+ * rounded once.  y must not be m (the residual block adds the ungated m afterwards).  cin 3 or 6, k x k = 3x3 or 5x5, stride 1, pads k/2,
+ * cout = 64*{1,2,4,8}; anything else returns VCG_E_UNSUPPORTED before any launch.  wfrag: vcg_conv_in_gate_bf16_wfrag_bytes(cin, kh, kw, cout)
+ * bytes (0 for an unsupported shape) made by vcg_pack_conv_in_gate_bf16 from Keras' (kh,kw,cin,cout) fp32 kernel.  No scratch memory. */
+size_t vcg_conv_in_gate_bf16_wfrag_bytes(int32_t cin, int32_t kh, int32_t kw, int32_t cout);
+int vcg_pack_conv_in_gate_bf16(const void* w_hwio, int32_t cin, int32_t kh, int32_t kw, int32_t cout, void* out, hipStream_t stream);
+int vcg_conv_in_gate_bf16_fwd(const vcg_conv_desc* d, const void* u, const void* wfrag, const void* bias, const void* m, void* y,
+                              hipStream_t stream);
+
+/* to_add_input of upsampling_block_attention (upscaling/upscaler/model.py:94-97), in place on the bf16 NHWC output y [n][s h][s w][cout] of the
+ * stage's LeakyReLU:  y = bf16(y + bias[c] + Conv2DTranspose(cout, s+1, strides s, 'same')(atanh(0.99999 x))[c]), x the fp32 NCHW frames
+ * [n][3][h][w], w_hwoi Keras' (s+1,s+1,cout,3) fp32 kernel (used as fp32), bias [cout] or NULL.  The atanh is evaluated in double as
+ * vcg_atanh_scale does.  d: cin 3, h x w the frames, oh = s h, ow = s w, kh = kw = s+1, stride = s in {2, 4}, pads 0 ('same' crops
+ * (k - s) / 2 = 0 in front), cout % 8 == 0 with the weights inside 64 KiB of LDS (cout <= 208 at s = 4); VCG_E_UNSUPPORTED otherwise.
+ * No scratch memory. */
+int vcg_input_convt_add_bf16(const vcg_conv_desc* d, const void* x, const void* w_hwoi, const void* bias, void* y, hipStream_t stream);
 /* data gradient of such a first layer from the bf16 NHWC gradient dz [n][oh][ow][64] in front of its activation to the fp32 NCHW gradient
  * of the frames [n][3][h][w] (what the generator's backward consumes): the 3-channel result is computed as 12 (4x4 stride 2: four sub-pixel
  * phases x 3) or 3 of 64 virtual output channels of a 3x3 stride-1 convolution over dz on vcg_conv2d_nhwc_bf16_fwd and scattered.

@@ -2,6 +2,10 @@
 (kernel_size 5, upscale_factor 4, 16 residual blocks; upscaling/upscaler/model.py:267) at 128 -> 512, batch 32, one hipGraph replay per
 batch.  Prints one JSON line per run, shaped like ``bench.py --config c5``'s.
 
+  --generator attention   the same for make_upscaler_attention (model.py:299-328, train_gan3.py's default -gm resnet-att) through its
+           to_inference_bf16(); --full then times one launch of each kind the pass makes and, for the memory-bound ones (the gates,
+           to_add_input), the bytes they must move per second next to vcg_norm_act_fwd_bf16 on the same tensor
+
   --fp32   also times the fp32 product path (G.forward, i.e. what G.predict runs per batch) on the same weights and frames; it may run a
            smaller batch per call (--fp32-batch), stated in its line
   --full   per-layer HIP-event times of the bf16 pass (the calls the engine makes, on its buffers), with algorithmic FLOP, TFLOP/s and the
@@ -46,6 +50,17 @@ def flop_frame(h, w, k, f, res):
     return t + flop_conv(1, hh, ww, 256, 3, 9)
 
 
+def flop_frame_attention(h, w, k, f, res):
+    """make_upscaler_attention: the trunk, one 3 -> 64 attention convolution per block, per stage a 6 -> cin attention convolution, the
+    ConvT to 128 channels and the (s+1)^2 x 3 -> 128 to_add_input transpose (at most 2 x 2 taps reach an output), final/conv on 128"""
+    t = flop_conv(1, h, w, 3, 64, 9) + (2 * res + 1) * flop_conv(1, h, w, 64, 64, k) + res * flop_conv(1, h, w, 3, 64, k)
+    hh, ww, cin, s = h, w, 64, 2
+    while s <= f:
+        t += flop_conv(1, hh, ww, 6, cin, k) + flop_convt(1, hh, ww, cin, 128, k) + 2.0 * h * w * 3 * 128 * (s + 1) ** 2
+        hh, ww, cin, s = 2 * hh, 2 * ww, 128, 2 * s
+    return t + flop_conv(1, hh, ww, 128, 3, 9)
+
+
 def time_events(fn, reps, warm=2):
     import torch
     for _ in range(warm):
@@ -73,6 +88,7 @@ def main():
     ap.add_argument("--fp32-batch", type=int, default=4)
     ap.add_argument("--full", action="store_true")
     ap.add_argument("--ab-reps", type=int, default=5)
+    ap.add_argument("--generator", choices=("orig", "attention"), default="orig")
     args = ap.parse_args()
 
     import torch
@@ -83,7 +99,9 @@ def main():
     h, B, k, f, res = args.lr_size, args.batch, args.kernel_size, args.upscale, args.res_blocks
     w = args.lr_width or h
     frame = "%dx%d->%dx%d" % (h, w, f * h, f * w)
-    G = PM.make_upscaler_orig((f * h, f * w, 3), kernel_size=k, upscale_factor=f, res_block_num=res, seed=7)
+    att = args.generator == "attention"
+    make = PM.make_upscaler_attention if att else PM.make_upscaler_orig
+    G = make((f * h, f * w, 3), kernel_size=k, upscale_factor=f, res_block_num=res, seed=7)
     inf = G.to_inference_bf16()
     rt = inf.rt
     g1 = torch.Generator().manual_seed(1234)
@@ -97,14 +115,14 @@ def main():
         inf.replay(x)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    fl = flop_frame(h, w, k, f, res)
+    fl = flop_frame_attention(h, w, k, f, res) if att else flop_frame(h, w, k, f, res)
     bf = {"metric": "upscaled frames/s (inference, generator only, bf16) at %s" % frame, "value": round(B * args.steps / dt, 2),
           "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
           "higher_is_better": True, "dtype": "bf16", "data": "synthetic",
           "gflop_per_frame": round(fl / 1e9, 1), "tflops": round(fl * B * args.steps / dt / 1e12, 1),
           "peak_share": round(fl * B * args.steps / dt / PEAK_BF16, 3),
-          "config": {"workload": "make_upscaler_orig((%d,%d,3),k=%d,x%d,res=%d).to_inference_bf16(), BN folded, bf16 NHWC activations, "
-                                 "fp32 accumulate, batch %d, one hipGraph replay per batch" % (f * h, f * w, k, f, res, B),
+          "config": {"workload": "%s((%d,%d,3),k=%d,x%d,res=%d).to_inference_bf16(), BN folded, bf16 NHWC activations, "
+                                 "fp32 accumulate, batch %d, one hipGraph replay per batch" % (make.__name__, f * h, f * w, k, f, res, B),
                      "global_batch": B, "frame": frame, "launch": "hipGraph replay"}}
     print(json.dumps(bf), flush=True)
 
@@ -129,7 +147,7 @@ def main():
                                                  "batch %d per call (eager launches)" % b32, "global_batch": b32, "frame": frame}}), flush=True)
 
     if args.full:
-        full(args, inf, x, h, w, k, f, res, B)
+        (full_attention if att else full)(args, inf, x, h, w, k, f, res, B)
 
 
 def full(args, inf, x, h, w, k, f, res, B):
@@ -189,6 +207,81 @@ def full(args, inf, x, h, w, k, f, res, B):
     ms = time_events(lambda: L.check(lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1,
                                                                   Bf["y"].data_ptr(), st), "final"), args.ab_reps)
     row("final/conv 9x9 256->3 at %dx%d, %d frames per launch" % (hh, ww, ch), ms, flop_conv(ch, hh, ww, 256, 3, 9))
+    for r in rows:
+        print(json.dumps(dict(r, kind="layer")), flush=True)
+
+
+def full_attention(args, inf, x, h, w, k, f, res, B):
+    """one launch of each kind the attention pass makes, on the engine's own buffers: HIP-event times, algorithmic FLOP, and for the
+    memory-bound kernels the bytes they must move (gate: m read + y written; to_add_input: y read + written) per second, next to
+    vcg_norm_act_fwd_bf16 (x read + y written) on the same tensor"""
+    import torch
+    from upscaler import _lib as L
+    rt, lib, st = inf.rt, inf.rt.lib, inf.rt.stream
+    Bf = inf._buffers(B, h, w)
+    inf.forward(x)                                    # the gates' inputs and every buffer hold a pass's data
+    torch.cuda.synchronize()
+    rows = []
+
+    def row(name, ms, flop=0.0, nbytes=0, extra=None):
+        d = {"layer": name, "ms": round(ms, 4)}
+        if flop:
+            d.update({"gflop": round(flop / 1e9, 2), "tflops": round(flop / ms / 1e9, 1), "peak_share": round(flop / (ms * 1e-3) / PEAK_BF16, 3)})
+        if nbytes:
+            d.update({"must_move_gb": round(nbytes / 1e9, 3), "tb_per_s": round(nbytes / (ms * 1e-3) / 1e12, 3)})
+        d.update(extra or {})
+        rows.append(d)
+
+    def norm_act(t):
+        """vcg_norm_act_fwd_bf16 on tensor t (scale 1, shift 0, no activation) into a buffer of its own: the streaming yardstick"""
+        n_, hh_, ww_, c_ = t.shape
+        one, zero = torch.ones(c_, device=rt.device), torch.zeros(c_, device=rt.device)
+        out = torch.empty_like(t)
+        ms = time_events(lambda: L.check(lib.vcg_norm_act_fwd_bf16(t.data_ptr(), n_, c_, hh_ * ww_, one.data_ptr(), zero.data_ptr(), 1, L.ACT_NONE, 0.0,
+                                                                    None, None, out.data_ptr(), st), "norm_act"), args.ab_reps)
+        return ms, 2 * t.numel() * 2
+
+    w0, b0, a0 = inf.first
+    d0 = L.ConvDesc(B, 3, h, w, 64, h, w, 9, 9, 1, 4, 4)
+    row("initial/conv 9x9 3->64", time_events(lambda: L.check(lib.vcg_conv9x9_from3_bf16_fwd(
+        ctypes.byref(d0), x.data_ptr(), w0.data_ptr(), b0.data_ptr(), a0.data_ptr(), Bf["skip"].data_ptr(), st), "first"), args.ab_reps),
+        flop_conv(B, h, w, 3, 64, 9))
+    if inf.trunk:
+        gate, w1, s1, h1, al = inf.trunk[0][:5]
+        ms = time_events(lambda: inf._gate(gate, x, 3, Bf["skip"], Bf["g"], B, h, w), args.ab_reps)
+        row("res_block gate %dx%d 3->64 (x%d per pass)" % (k, k, res), ms, flop_conv(B, h, w, 3, 64, k), 2 * Bf["g"].numel() * 2)
+        msn, nb = norm_act(Bf["skip"])
+        row("  vcg_norm_act_fwd_bf16 on the same tensor", msn, 0.0, nb, {"gate_rate_vs_norm_act": round(msn / ms, 2)})
+        row("res_block conv %dx%d 64->64 + BN + PReLU (x%d per pass)" % (k, k, 2 * res + 1),
+            time_events(lambda: inf._conv(Bf["g"], w1, Bf["b"], s1, h1, L.ACT_PRELU, al, None, B, h, w), args.ab_reps), flop_conv(B, h, w, 64, 64, k))
+    ch, crop = Bf["chunk"], max(k - 2, 0) // 2
+    src, hh, ww = Bf["a"][:ch], h, w
+    for i, ((gate, wt, bt, slope, cin, cout, wa, ba), stg) in enumerate(zip(inf.ups, Bf["stages"])):
+        scale = 2 ** (i + 1)
+        u = stg["u"][:ch]
+        ms = time_events(lambda: inf._gate(gate, u, 6, src, stg["g"], ch, hh, ww), args.ab_reps)
+        row("upscaling/%d gate %dx%d 6->%d at %dx%d, %d frames per launch" % (i, k, k, cin, hh, ww, ch), ms, flop_conv(ch, hh, ww, 6, cin, k),
+            2 * stg["g"].numel() * 2)
+        msn, nb = norm_act(stg["g"])
+        row("  vcg_norm_act_fwd_bf16 on the same tensor", msn, 0.0, nb, {"gate_rate_vs_norm_act": round(msn / ms, 2)})
+        dt = L.ConvDesc(ch, cin, hh, ww, cout, 2 * hh, 2 * ww, k, k, 2, crop, crop)
+        row("upscaling/%d ConvT %dx%d s2 %d->%d at %dx%d" % (i, k, k, cin, cout, 2 * hh, 2 * ww),
+            time_events(lambda: L.check(lib.vcg_conv_transpose2d_nhwc_bf16_fwd(ctypes.byref(dt), stg["g"].data_ptr(), wt.data_ptr(), bt.data_ptr(),
+                                                                               L.ACT_LRELU, slope, stg["y"].data_ptr(), st), "convT"), args.ab_reps),
+            flop_convt(ch, hh, ww, cin, cout, k))
+        da = L.ConvDesc(ch, 3, h, w, cout, scale * h, scale * w, scale + 1, scale + 1, scale, 0, 0)
+        ms = time_events(lambda: L.check(lib.vcg_input_convt_add_bf16(ctypes.byref(da), x.data_ptr(), wa.data_ptr(), ba.data_ptr(), stg["y"].data_ptr(), st),
+                                         "to_add"), args.ab_reps)
+        row("upscaling/%d to_add_input (ConvT %dx%d s%d of atanh) at %dx%d" % (i, scale + 1, scale + 1, scale, 2 * hh, 2 * ww), ms, 0.0,
+            2 * stg["y"].numel() * 2)
+        msn, nb = norm_act(stg["y"])
+        row("  vcg_norm_act_fwd_bf16 on the same tensor", msn, 0.0, nb, {"to_add_rate_vs_norm_act": round(msn / ms, 2)})
+        src, hh, ww = stg["y"], 2 * hh, 2 * ww
+    wf, bf_, cfin = inf.final
+    df = L.ConvDesc(ch, cfin, hh, ww, 3, hh, ww, 9, 9, 1, 4, 4)
+    row("final/conv 9x9 %d->3 at %dx%d, %d frames per launch" % (cfin, hh, ww, ch),
+        time_events(lambda: L.check(lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, Bf["y"].data_ptr(), st),
+                                    "final"), args.ab_reps), flop_conv(ch, hh, ww, cfin, 3, 9))
     for r in rows:
         print(json.dumps(dict(r, kind="layer")), flush=True)
 

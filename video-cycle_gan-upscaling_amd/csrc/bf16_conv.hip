@@ -750,13 +750,16 @@ __global__ __launch_bounds__(V2_NT, 1) void conv3x3_c64_bf16_v2_kernel(C3Params 
 // stride S): 9x9 stride 1 above (KH 9, NG 3), the critics' first layers -- 4x4 stride 2 (PatchGAN block 1: KH 4, NG 1, S 2) and 3x3 stride 1
 // (simple_512 / thin_512 block 1, model.py:839: KH 3, NG 1) -- with bias + LeakyReLU / PReLU in the epilogue.  An output tile of 12x32
 // pixels reads a halo of (12 S + KH - S) x (31 S + 4 NG + 1) input pixels; lane r's fragment sits at column r S + 4 j + 2 hh.
-template <int KH, int NG, int S>
+// NSRC (the input-driven gates below): the input is NSRC stacked 3-channel sources, fp32 NCHW [n][3 NSRC][h][w]; each source has a halo tile
+// of its own in LDS (XB1 bytes apart) and its own KH x NG k-steps -- the convolution is linear in its input channels.
+template <int KH, int NG, int S, int NSRC = 1>
 struct I3Cfg {
     static constexpr int HR = TR * S + KH - S;                    // halo rows           (9x9: 20)
     static constexpr int HC = (31 * S + 4 * NG + 2) & ~1;         // halo columns, even  (9x9: 44)
     static constexpr int ROWB = HC * 8;
-    static constexpr int XB = (HR * ROWB + 15) & ~15;             // 9x9: 7040 B
-    static constexpr int NK = KH * NG;                            // k-steps of 16
+    static constexpr int XB1 = (HR * ROWB + 15) & ~15;            // one source's halo tile (9x9: 7040 B)
+    static constexpr int XB = NSRC * XB1;
+    static constexpr int NK = NSRC * KH * NG;                     // k-steps of 16
     static constexpr int WB = NK * 64 * 32;                       // 9x9: 55296 B: [k-step][out-channel][half][8 bf16]
     static constexpr int NPIX = HR * HC;                          // 9x9: 880 pixels per halo tile
     static constexpr int NPRE = (NPIX + NLW * 64 - 1) / (NLW * 64);       // pixels per loader lane (9x9: 7)
@@ -770,7 +773,8 @@ struct I9Params {
     const float* alpha;      // PReLU slopes [cout] or null (none)
     __bf16* y;               // bf16 NHWC [n][h][w][cout]
     __bf16* z;               // optional bf16 NHWC [n][h][w][cout]: the value in front of the PReLU (its backward needs the sign and, for the slope gradient, the value)
-    const __bf16* mask;      // optional bf16 NHWC [n][h][w][cout]: y *= (mask > 0 ? 1 : mask_slope)  (data gradient in front of a LeakyReLU)
+    const __bf16* mask;      // optional bf16 NHWC [n][h][w][cout]: y *= (mask > 0 ? 1 : mask_slope)  (data gradient in front of a LeakyReLU);
+                             // GATE instantiations: the gated tensor m, y = sigmoid(conv + bias) * m
     float mask_slope;
     float* chsum;            // optional [workgroups per channel block * 6][cout]: per-wave sums of the stored output per channel (a bias gradient)
     int n, h, w_, cout, tiles_x, tiles_y, total;        // cout = 64 * nblk; workgroup b serves channel block b % nblk; h, w_: INPUT size
@@ -812,10 +816,19 @@ __device__ unsigned long long vcg_i9_stamp_sums[512 * 8 * 6];
 #define I9_ADD(sum, a, b) do { } while (0)
 #endif
 
-template <int KH, int NG, int S>
+// sigmoid from one v_exp_f32 and one v_rcp_f32 (as fast_tanh below): 1 / (1 + exp(-x)).  exp(-x) carries the rounding of x log2(e) and the
+// 1-ulp v_exp_f32, a relative error below 2^-24 (2 + 1.5 |x|); the sigmoid's absolute error is s (1 - s) times that, <= 3e-7 for every x
+// (s (1 - s) |x| <= 0.23) -- four orders below the bf16 rounding of the product it feeds (up to 2^-8 relative).  Saturates cleanly: exp -> inf
+// gives rcp(inf) = 0, exp -> 0 gives 1.
+__device__ __forceinline__ float fast_sigmoid(float x) { return __frcp_rn(1.f + __expf(-x)); }
+
+// GATE (input-driven attention gates of make_upscaler_attention, model.py:33-36, 86-90): the epilogue is y = bf16(sigmoid(conv + bias) * m)
+// with m (p.mask) a bf16 NHWC tensor of the output's shape, requested under the MFMA loop like the LeakyReLU mask; the attention tensor
+// itself never leaves the registers.
+template <int KH, int NG, int S, int NSRC = 1, bool GATE = false>
 __global__ __launch_bounds__(NT, 1) void conv_c3to64_bf16_kernel(I9Params p) {
-    using C = I3Cfg<KH, NG, S>;
-    constexpr int I_HC = C::HC, I_ROWB = C::ROWB, I_XB = C::XB, I_WB = C::WB, I_NPIX = C::NPIX, I_NPRE = C::NPRE, NK = C::NK;
+    using C = I3Cfg<KH, NG, S, NSRC>;
+    constexpr int I_HC = C::HC, I_ROWB = C::ROWB, I_XB = C::XB, I_XB1 = C::XB1, I_WB = C::WB, I_NPIX = C::NPIX, I_NPRE = C::NPRE, NK = C::NK;
 #ifdef VCG_I9_STAMPS
     unsigned long long s0 = 0, s1 = 0, s2 = 0, s3 = 0, ntl = 0, st0, st1, st2, st3, st4;
     const unsigned long long k_c0 = __builtin_amdgcn_s_memtime();
@@ -839,11 +852,11 @@ __global__ __launch_bounds__(NT, 1) void conv_c3to64_bf16_kernel(I9Params p) {
 
     if (wv >= NCW) {
         const int lt = tid - NCW * 64;
-        float pre[I_NPRE][3];
+        float pre[NSRC][I_NPRE][3];
         auto fetch = [&](int tile) {
             const int txi = tile % p.tiles_x, t2 = tile / p.tiles_x, tyi = t2 % p.tiles_y, img = t2 / p.tiles_y;
             const int y0 = tyi * TR * S - p.pad_top, x0 = txi * TC * S - p.pad_left;
-            const float* xi = p.x + (long)img * 3 * plane;
+            const float* xi = p.x + (long)img * (3 * NSRC) * plane;
 #pragma unroll
             for (int i = 0; i < I_NPRE; ++i) {
                 const int pix = min(lt + NLW * 64 * i, I_NPIX - 1);
@@ -852,23 +865,27 @@ __global__ __launch_bounds__(NT, 1) void conv_c3to64_bf16_kernel(I9Params p) {
                 const bool ok = (unsigned)gy < (unsigned)p.h && (unsigned)gx < (unsigned)p.w_;
                 const long o = (long)min(max(gy, 0), p.h - 1) * p.w_ + min(max(gx, 0), p.w_ - 1);
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    const float v = xi[ch * plane + o];
-                    pre[i][ch] = ok ? v : 0.f;
-                }
+                for (int sc = 0; sc < NSRC; ++sc)
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) {
+                        const float v = xi[(sc * 3 + ch) * plane + o];
+                        pre[sc][i][ch] = ok ? v : 0.f;
+                    }
             }
         };
         auto stash = [&]() {
 #pragma unroll
-            for (int i = 0; i < I_NPRE; ++i) {
-                const int pix = min(lt + NLW * 64 * i, I_NPIX - 1);
-                bf16x4 v;
-                v[0] = (__bf16)pre[i][0];
-                v[1] = (__bf16)pre[i][1];
-                v[2] = (__bf16)pre[i][2];
-                v[3] = (__bf16)0.f;
-                *(bf16x4*)(xl + pix * 8) = v;
-            }
+            for (int sc = 0; sc < NSRC; ++sc)
+#pragma unroll
+                for (int i = 0; i < I_NPRE; ++i) {
+                    const int pix = min(lt + NLW * 64 * i, I_NPIX - 1);
+                    bf16x4 v;
+                    v[0] = (__bf16)pre[sc][i][0];
+                    v[1] = (__bf16)pre[sc][i][1];
+                    v[2] = (__bf16)pre[sc][i][2];
+                    v[3] = (__bf16)0.f;
+                    *(bf16x4*)(xl + sc * I_XB1 + pix * 8) = v;
+                }
         };
         int tile = wg0;
         if (tile < p.total) fetch(tile);
@@ -915,7 +932,7 @@ __global__ __launch_bounds__(NT, 1) void conv_c3to64_bf16_kernel(I9Params p) {
         // under the MFMA loop.  (Loaded where it was used, each of the eight 16-byte loads waited out an HBM round trip: 6.6k of a tile's
         // 21k cycles, profiles/r03_i9_stamps.txt.)
         bf16x8 mk[2][2][2];
-        if (p.mask) {
+        if (GATE || p.mask) {
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -938,11 +955,11 @@ __global__ __launch_bounds__(NT, 1) void conv_c3to64_bf16_kernel(I9Params p) {
 
         bf16x8 fa[2][2], fb[2][2];
         auto frag = [&](auto ic) {
-            constexpr int i = decltype(ic)::value, ky = i / NG, j = i - NG * ky, buf = i & 1;
+            constexpr int i = decltype(ic)::value, sc = i / (KH * NG), i1 = i - sc * (KH * NG), ky = i1 / NG, j = i1 - NG * ky, buf = i & 1;
             const unsigned char* wa = wl + i * 2048 + aoff;
             fa[buf][0] = *(const bf16x8*)(wa);
             fa[buf][1] = *(const bf16x8*)(wa + 1024);
-            const unsigned char* b0 = xb + ky * I_ROWB + j * 32;
+            const unsigned char* b0 = xb + sc * I_XB1 + ky * I_ROWB + j * 32;
             bf16x4 lo = *(const bf16x4*)(b0), hi = *(const bf16x4*)(b0 + 8);
             fb[buf][0] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
             lo = *(const bf16x4*)(b0 + S * I_ROWB);
@@ -993,13 +1010,17 @@ __global__ __launch_bounds__(NT, 1) void conv_c3to64_bf16_kernel(I9Params p) {
                     for (int j = 0; j < 8; ++j) {
                         float u = v[j] + sh[j];
                         zv[j] = (__bf16)u;
-                        u = u >= 0.f ? u : u * al[j];
-                        if (p.mask) u = (float)mk[mt][q][pt][j] > 0.f ? u : u * p.mask_slope;
+                        if constexpr (GATE) {
+                            u = fast_sigmoid(u) * (float)mk[mt][q][pt][j];           // fp32 product, rounded once
+                        } else {
+                            u = u >= 0.f ? u : u * al[j];
+                            if (p.mask) u = (float)mk[mt][q][pt][j] > 0.f ? u : u * p.mask_slope;
+                        }
                         ov[j] = (__bf16)u;
                     }
                     if (ok) *(bf16x8*)(p.y + o) = ov;
-                    if (p.z && ok) *(bf16x8*)(p.z + o) = zv;
-                    if (p.chsum && ok) {                             // the values as stored
+                    if (!GATE && p.z && ok) *(bf16x8*)(p.z + o) = zv;
+                    if (!GATE && p.chsum && ok) {                             // the values as stored
 #pragma unroll
                         for (int j = 0; j < 8; ++j) csum[mt * 16 + q * 8 + j] += (float)ov[j];
                     }
@@ -1019,7 +1040,7 @@ __global__ __launch_bounds__(NT, 1) void conv_c3to64_bf16_kernel(I9Params p) {
         o[0] = s0, o[1] = s1, o[2] = s2, o[3] = s3, o[4] = ntl, o[5] = __builtin_amdgcn_s_memtime() - k_c0;
     }
 #endif
-    if (p.chsum) {
+    if (!GATE && p.chsum) {
         // lane (r, hh) ends up with the sum of value r = [mt][q][j] over the wave's 32 pixel lanes: channel mt*32 + 16q + 8hh + j
         const float t = half_wave_reduce_scatter32(csum, r);
         p.chsum[(long)(wg0 * NCW + wv) * p.cout + cb * 64 + (r >> 4) * 32 + ((r >> 3) & 1) * 16 + 8 * hh + (r & 7)] = t;
@@ -1316,7 +1337,7 @@ __global__ __launch_bounds__(NT, 1) void convt3x3_c64_bf16_kernel(CTParams p) {
 //   * work item = (image, 64-column strip, segment of 32..128 output rows); 2 workgroups per CU.
 constexpr int F_PIX = 72;                    // 64 output columns + 4 + 4
 constexpr int F_ROWB = F_PIX * 128;          // one wave's slice of one input row in LDS (9216 B)
-constexpr int F_LDS = 4 * 2 * F_ROWB + 2 * 4 * 3 * 64 * 4;
+// LDS of a workgroup of NW waves: NW * 2 * F_ROWB (row slices, double buffered) + 2 * NW * 3 * 64 * 4 (partial output rows)
 constexpr int F9_MAX_GRID = 512;             // workgroups of one launch: two per CU
 constexpr int F_NFRAG = 4 * 9 * 4 * 64;      // 16-byte weight fragments; the packed buffer holds 4 more (zeros)
 
@@ -1360,8 +1381,13 @@ __device__ __forceinline__ float fast_tanh(float x) {
 // lane constants; the pointer form (BUF = false: images too large for a descriptor) keeps nine 64-bit lane addresses, which at this kernel's
 // 256-register budget are SPILLED -- hipcc then waits vmcnt(0) in front of every reload, i.e. for every earlier piece of the row: the nine
 // pieces went out one HBM round trip after the other, 8.0 k of the 15.4 k cycles of a row (profiles/r03_f9_stamps.txt).
-template <bool BUF>
-__global__ __launch_bounds__(256, 2) void conv9x9_c256to3_bf16_kernel(F9Params p) {
+// NW: waves per workgroup = input channels / 64 (the channel split): 4 for the 256-channel final/conv of make_upscaler_orig, 2 for the
+// 128-channel one of make_upscaler_attention (model.py:326).  A wave keeps its 64 channels, its 144 weight registers and its row slice
+// either way; a pixel is NW x 128 bytes, the workgroup NW x 64 threads and NW x 18 KiB of row buffers (so twice as many fit a CU), and
+// the NW partial rows meet in LDS as before.
+template <bool BUF, int NW = 4>
+__global__ __launch_bounds__(64 * NW, 2) void conv9x9_c256to3_bf16_kernel(F9Params p) {
+    constexpr int PB = NW * 128;                                      // bytes per pixel
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long f0 = 0, f1 = 0, f2 = 0, f3 = 0, f4 = 0, f5 = 0, f6 = 0, fs_shift = 0, fs_wait = 0, fs_dma = 0, fs_mfma = 0, fs_bar = 0, fs_out = 0, f_rows = 0;
     (void)f6, (void)fs_shift, (void)f0, (void)f1, (void)f2, (void)f3, (void)f4, (void)f5, (void)fs_wait, (void)fs_dma, (void)fs_mfma, (void)fs_bar, (void)fs_out, (void)f_rows;
@@ -1371,7 +1397,7 @@ __global__ __launch_bounds__(256, 2) void conv9x9_c256to3_bf16_kernel(F9Params p
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
     const int c = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave = input-channel chunk
     unsigned char* rowbuf = smem + c * 2 * F_ROWB;
-    float* part = (float*)(smem + 4 * 2 * F_ROWB);                    // [2][4][3][64]
+    float* part = (float*)(smem + NW * 2 * F_ROWB);                   // [2][NW][3][64]
 
     // weights: 36 fragments of 16 B per lane
     bf16x8 wf[9][4];
@@ -1393,13 +1419,16 @@ __global__ __launch_bounds__(256, 2) void conv9x9_c256to3_bf16_kernel(F9Params p
     // (slot & 7) ^ f(pixel)
     // (recomputed per row from three lane constants: 18 more live VGPRs would spill)
     const int l3 = lane >> 3, l4 = lane >> 4, l7 = lane & 7;
-    const float bias = (p.bias && tid < 192) ? p.bias[tid >> 6] : 0.f;
-    const unsigned char* zeros = (const unsigned char*)(p.wfrag + F_NFRAG);      // padding pixels are fetched from here
+    float bias = 0.f, bias3[3] = {0.f, 0.f, 0.f};
+    if constexpr (NW == 4) bias = (p.bias && tid < 192) ? p.bias[tid >> 6] : 0.f;
+    else if (p.bias) bias3[0] = p.bias[0], bias3[1] = p.bias[1], bias3[2] = p.bias[2];
+    (void)bias, (void)bias3;
+    const unsigned char* zeros = (const unsigned char*)(p.wfrag + NW * (F_NFRAG / 4));      // padding pixels are fetched from here
     // BUF: byte offset of this lane's slot of piece k relative to the piece's first pixel: pixel l3, source chunk of parity k & 1
     unsigned lc[2];
 #pragma unroll
-    for (int par = 0; par < 2; ++par) lc[par] = (unsigned)(l3 * 512 + (c * 8 + (l7 ^ ((4 * par + l4) & 7))) * 16);
-    const long img_bytes = (long)p.h * p.w_ * 512;
+    for (int par = 0; par < 2; ++par) lc[par] = (unsigned)(l3 * PB + (c * 8 + (l7 ^ ((4 * par + l4) & 7))) * 16);
+    const long img_bytes = (long)p.h * p.w_ * PB;
 
     for (int item = blockIdx.x; item < p.total; item += gridDim.x) {
         const int seg = item % p.segs, i2 = item / p.segs, strip = i2 % p.strips, img = i2 / p.strips;
@@ -1410,11 +1439,11 @@ __global__ __launch_bounds__(256, 2) void conv9x9_c256to3_bf16_kernel(F9Params p
             if (BUF) {
                 // offset = (row, first pixel of the strip's halo) + piece + lane constant, in 32-bit wrap-around arithmetic: a row above the
                 // image lands just below 4 GiB, a row below it just past the image -- both outside the descriptor (host guard)
-                const unsigned row_off = (unsigned)(yi * p.w_ + x0 - 4) * 512u;
+                const unsigned row_off = (unsigned)(yi * p.w_ + x0 - 4) * (unsigned)PB;
 #pragma unroll
                 for (int k = 0; k < 9; ++k) {
                     const int gx = x0 - 4 + k * 8 + l3;
-                    unsigned off = row_off + (unsigned)(k * 4096) + lc[k & 1];
+                    unsigned off = row_off + (unsigned)(k * 8 * PB) + lc[k & 1];
                     asm volatile("" : "+v"(off));                    // a select, not a branch around the arithmetic
                     off = (unsigned)gx < (unsigned)p.w_ ? off : VCG_OOB;
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (void __attribute__((address_space(3)))*)(rowbuf + buf * F_ROWB + k * 1024), 16, off, 0, 0, 0);
@@ -1422,13 +1451,13 @@ __global__ __launch_bounds__(256, 2) void conv9x9_c256to3_bf16_kernel(F9Params p
                 return;
             }
             const bool rowok = (unsigned)yi < (unsigned)p.h;
-            const unsigned char* rowp = p.x + ((long)(img * p.h + (rowok ? yi : 0)) * p.w_) * 512;
+            const unsigned char* rowp = p.x + ((long)(img * p.h + (rowok ? yi : 0)) * p.w_) * PB;
 #pragma unroll
             for (int k = 0; k < 9; ++k) {
                 const int gx = x0 - 4 + k * 8 + l3;
                 const bool ok = rowok && (unsigned)gx < (unsigned)p.w_;
                 const int dsrc = (c * 8 + (l7 ^ ((4 * k + l4) & 7))) * 16;
-                const unsigned char* src = ok ? rowp + (long)gx * 512 + dsrc : zeros;
+                const unsigned char* src = ok ? rowp + (long)gx * PB + dsrc : zeros;
                 __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
                                                  (void __attribute__((address_space(3)))*)(rowbuf + buf * F_ROWB + k * 1024), 16, 0, 0);
             }
@@ -1498,7 +1527,7 @@ __global__ __launch_bounds__(256, 2) void conv9x9_c256to3_bf16_kernel(F9Params p
             // finished output row yo = yi - 4: this wave's partial (its 64 input channels) -> LDS
             const int yo = yi - 4, slot = yo & 1;
             if (yo >= y0) {
-                float* pp = part + ((slot * 4 + c) * 3) * 64;
+                float* pp = part + ((slot * NW + c) * 3) * 64;
 #pragma unroll
                 for (int tt = 0; tt < 2; ++tt) {
                     // rows 3 / 7 / 11 = co 0 (lower half) / 1 (upper half) / 2 (lower half): every lane stores register 3 to its co's row, the
@@ -1513,12 +1542,26 @@ __global__ __launch_bounds__(256, 2) void conv9x9_c256to3_bf16_kernel(F9Params p
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             F9_STAMP(f4);
-            if (yo >= y0 && tid < 192) {
-                const int co = tid >> 6, col = tid & 63;
-                const float* q = part + slot * 4 * 3 * 64 + co * 64 + col;
-                float v = ((q[0] + q[3 * 64]) + (q[2 * 3 * 64] + q[3 * 3 * 64])) + bias;
-                if (p.tanh_act) v = fast_tanh(v);
-                if (x0 + col < p.w_) p.y[((long)(img * 3 + co) * p.h + yo) * p.w_ + x0 + col] = v;
+            if constexpr (NW == 4) {
+                if (yo >= y0 && tid < 192) {
+                    const int co = tid >> 6, col = tid & 63;
+                    const float* q = part + slot * 4 * 3 * 64 + co * 64 + col;
+                    float v = ((q[0] + q[3 * 64]) + (q[2 * 3 * 64] + q[3 * 3 * 64])) + bias;
+                    if (p.tanh_act) v = fast_tanh(v);
+                    if (x0 + col < p.w_) p.y[((long)(img * 3 + co) * p.h + yo) * p.w_ + x0 + col] = v;
+                }
+            } else if (yo >= y0) {
+                // 3 x 64 outputs of the row on NW x 64 threads
+                for (int o = tid; o < 192; o += 64 * NW) {
+                    const int co = o >> 6, col = o & 63;
+                    const float* q = part + slot * NW * 3 * 64 + co * 64 + col;
+                    float v = q[0];
+#pragma unroll
+                    for (int k = 1; k < NW; ++k) v += q[k * 3 * 64];
+                    v += co == 0 ? bias3[0] : co == 1 ? bias3[1] : bias3[2];
+                    if (p.tanh_act) v = fast_tanh(v);
+                    if (x0 + col < p.w_) p.y[((long)(img * 3 + co) * p.h + yo) * p.w_ + x0 + col] = v;
+                }
             }
             F9_STAMP(f5);
             F9_ADD(fs_wait, f0, f1); F9_ADD(fs_dma, f1, f6); F9_ADD(fs_shift, f6, f2); F9_ADD(fs_mfma, f2, f3); F9_ADD(fs_bar, f3, f4); F9_ADD(fs_out, f4, f5);
@@ -1535,11 +1578,12 @@ __global__ __launch_bounds__(256, 2) void conv9x9_c256to3_bf16_kernel(F9Params p
 #endif
 }
 
-__global__ void pack_final9x9_kernel(const float* __restrict__ w, uint4* __restrict__ out) {
-    // w: Keras (9,9,256,3) -> out[chunk][kx][s][lane] = 8 bf16: A[row = lane&31][k = 8*(lane>>5) + j] of k-step (kx, s)
+__global__ void pack_final9x9_kernel(const float* __restrict__ w, uint4* __restrict__ out, int cin) {
+    // w: Keras (9,9,cin,3) -> out[chunk][kx][s][lane] = 8 bf16: A[row = lane&31][k = 8*(lane>>5) + j] of k-step (kx, s)
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= F_NFRAG + 4) return;
-    if (idx >= F_NFRAG) {
+    const int nfrag = (cin >> 6) * (F_NFRAG / 4);
+    if (idx >= nfrag + 4) return;
+    if (idx >= nfrag) {
         out[idx] = make_uint4(0, 0, 0, 0);
         return;
     }
@@ -1552,21 +1596,41 @@ __global__ void pack_final9x9_kernel(const float* __restrict__ w, uint4* __restr
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int ci = c * 64 + 16 * s + 8 * h + j;
-        v[j] = (__bf16)(ky >= 0 ? w[((ky * 9 + kx) * 256 + ci) * 3 + co] : 0.f);
+        v[j] = (__bf16)(ky >= 0 ? w[((ky * 9 + kx) * cin + ci) * 3 + co] : 0.f);
+    }
+    out[idx] = __builtin_bit_cast(uint4, v);
+}
+
+__global__ void pack_in_gate_kernel(const float* __restrict__ w, uint4* __restrict__ out, int cin, int cout, int kh, int kw, int ng) {
+    // w: Keras (kh,kw,cin,cout), cin = 3 nsrc -> out[channel block][k-step = (src*kh + ky)*ng + j][co in block][half] = 8 bf16:
+    // (kx = 4j+2*half, RGB0 of source src), (kx+1, RGB0 of source src); kernel columns past kw carry zeros
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int nk = (cin / 3) * kh * ng;
+    if (idx >= (cout >> 6) * nk * 64 * 2) return;
+    const int h = idx & 1, co = (idx >> 1) & 63, ks = (idx >> 7) % nk, cb = idx / (nk * 128);
+    const int src = ks / (kh * ng), k1 = ks - src * kh * ng, ky = k1 / ng, j = k1 - ng * ky;
+    const int m = cb * 64 + co;
+    bf16x8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int kx = 4 * j + 2 * h + (e >> 2), c = e & 3;
+        float x = 0.f;
+        if (kx < kw && c < 3) x = w[((ky * kw + kx) * cin + src * 3 + c) * cout + m];
+        v[e] = (__bf16)x;
     }
     out[idx] = __builtin_bit_cast(uint4, v);
 }
 
 }  // namespace
 
-template <int KH, int NG, int S>
+template <int KH, int NG, int S, int NSRC = 1, bool GATE = false>
 static int launch_conv3ch(I9Params p, hipStream_t stream) {
-    using C = I3Cfg<KH, NG, S>;
-    if (int e = vcg_allow_dyn_lds((const void*)conv_c3to64_bf16_kernel<KH, NG, S>, C::LDS)) return e;
+    using C = I3Cfg<KH, NG, S, NSRC>;
+    if (int e = vcg_allow_dyn_lds((const void*)conv_c3to64_bf16_kernel<KH, NG, S, NSRC, GATE>, C::LDS)) return e;
     const int nblk = p.cout / 64;
     int per = 1024 / nblk;
     if (per > p.total) per = p.total;
-    conv_c3to64_bf16_kernel<KH, NG, S><<<per * nblk, NT, C::LDS, stream>>>(p);
+    conv_c3to64_bf16_kernel<KH, NG, S, NSRC, GATE><<<per * nblk, NT, C::LDS, stream>>>(p);
     VCG_LAUNCH_CHECK();
     return VCG_OK;
 }
@@ -1759,7 +1823,22 @@ int vcg_conv_transpose2d_bf16_fwd(const vcg_conv_desc* d, const void* x, const v
 int vcg_pack_final9x9_bf16(const void* w, void* out, hipStream_t stream) {
     VCG_CHECK_PTR(w);
     VCG_CHECK_PTR(out);
-    pack_final9x9_kernel<<<(F_NFRAG + 4 + 255) / 256, 256, 0, stream>>>((const float*)w, (uint4*)out);
+    pack_final9x9_kernel<<<(F_NFRAG + 4 + 255) / 256, 256, 0, stream>>>((const float*)w, (uint4*)out, 256);
+    VCG_LAUNCH_CHECK();
+    return VCG_OK;
+}
+
+size_t vcg_conv9x9_to3_bf16_wfrag_bytes(int32_t cin) {
+    if (cin != 128 && cin != 256) return 0;
+    return (size_t)((cin >> 6) * (F_NFRAG / 4) + 4) * 16;
+}
+
+int vcg_pack_conv9x9_to3_bf16(const void* w, int32_t cin, void* out, hipStream_t stream) {
+    VCG_CHECK_PTR(w);
+    VCG_CHECK_PTR(out);
+    if (cin != 128 && cin != 256) return VCG_E_UNSUPPORTED;
+    const int total = (cin >> 6) * (F_NFRAG / 4) + 4;
+    pack_final9x9_kernel<<<(total + 255) / 256, 256, 0, stream>>>((const float*)w, (uint4*)out, cin);
     VCG_LAUNCH_CHECK();
     return VCG_OK;
 }
@@ -1771,7 +1850,9 @@ int vcg_conv9x9_to3_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* 
     VCG_CHECK_PTR(wfrag);
     VCG_CHECK_PTR(y);
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->oh != d->h || d->ow != d->w) return VCG_E_SHAPE;
-    if (d->cin != 256 || d->cout != 3 || d->kh != 9 || d->kw != 9 || d->stride != 1 || d->pad_top != 4 || d->pad_left != 4) return VCG_E_UNSUPPORTED;
+    if ((d->cin != 256 && d->cin != 128) || d->cout != 3 || d->kh != 9 || d->kw != 9 || d->stride != 1 || d->pad_top != 4 || d->pad_left != 4) return VCG_E_UNSUPPORTED;
+    const int nw = d->cin / 64;
+    const int max_grid = F9_MAX_GRID * 4 / nw;                    // half the threads and LDS per workgroup: twice the workgroups per CU
     F9Params p;
     p.x = (const unsigned char*)x;
     p.wfrag = (const uint4*)wfrag;
@@ -1790,20 +1871,22 @@ int vcg_conv9x9_to3_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* 
         for (int segs = 1; segs <= ceil_div(d->h, 16); ++segs) {
             const int sh = ceil_div(d->h, segs);
             if (ceil_div(d->h, sh) != segs) continue;                             // (the same height reached with fewer segments)
-            const long items = (long)colstrips * segs, rounds = (items + F9_MAX_GRID - 1) / F9_MAX_GRID, cost = rounds * (sh + 8);
+            const long items = (long)colstrips * segs, rounds = (items + max_grid - 1) / max_grid, cost = rounds * (sh + 8);
             if (best < 0 || cost < best) { best = cost; p.sh = sh; p.segs = segs; }
         }
     }
     p.total = p.n * p.strips * p.segs;
     p.tanh_act = tanh_act;
-    const int grid = p.total < F9_MAX_GRID ? p.total : F9_MAX_GRID;
+    const int grid = p.total < max_grid ? p.total : max_grid;
     // the descriptor form needs the image, four rows above and four below it inside 32-bit offsets
-    const bool buf = ((long)d->h + 8) * d->w * 512 + 65536 <= 0xFFFFFFE0l;
-#define VCG_F9_LAUNCH(BUF) do {                                                                                            \
-        if (int e = vcg_allow_dyn_lds((const void*)conv9x9_c256to3_bf16_kernel<BUF>, F_LDS)) return e;                    \
-        conv9x9_c256to3_bf16_kernel<BUF><<<grid, 256, F_LDS, stream>>>(p);                                                \
+    const bool buf = ((long)d->h + 8) * d->w * (nw * 128) + 65536 <= 0xFFFFFFE0l;
+#define VCG_F9_LAUNCH(BUF, NW) do {                                                                                        \
+        constexpr int lds = NW * 2 * F_ROWB + 2 * NW * 3 * 64 * 4;                                                         \
+        if (int e = vcg_allow_dyn_lds((const void*)conv9x9_c256to3_bf16_kernel<BUF, NW>, lds)) return e;                  \
+        conv9x9_c256to3_bf16_kernel<BUF, NW><<<grid, 64 * NW, lds, stream>>>(p);                                           \
     } while (0)
-    if (buf) VCG_F9_LAUNCH(true); else VCG_F9_LAUNCH(false);
+    if (nw == 4) { if (buf) VCG_F9_LAUNCH(true, 4); else VCG_F9_LAUNCH(false, 4); }
+    else { if (buf) VCG_F9_LAUNCH(true, 2); else VCG_F9_LAUNCH(false, 2); }
 #undef VCG_F9_LAUNCH
     VCG_LAUNCH_CHECK();
     return VCG_OK;
@@ -1909,6 +1992,59 @@ int vcg_conv3ch_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* wfra
     p.total = p.n * p.tiles_x * p.tiles_y;
     if (d->kh == 4) return launch_conv3ch<4, 1, 2>(p, stream);
     return launch_conv3ch<3, 1, 1>(p, stream);
+}
+
+// Input-driven sigmoid gate (residual_block_attention model.py:33-36, upsampling_block_attention :80-90): y = sigmoid(conv_kxk(u) + bias) * m
+static bool in_gate_supported(int cin, int kh, int kw, int cout) {
+    const int nblk = cout / 64;
+    return (cin == 3 || cin == 6) && kh == kw && (kh == 3 || kh == 5) && cout > 0 && cout % 64 == 0 && nblk <= 8 && !(nblk & (nblk - 1));
+}
+
+size_t vcg_conv_in_gate_bf16_wfrag_bytes(int32_t cin, int32_t kh, int32_t kw, int32_t cout) {
+    if (!in_gate_supported(cin, kh, kw, cout)) return 0;
+    return (size_t)(cout >> 6) * (cin / 3) * kh * ceil_div(kw, 4) * 64 * 2 * 16;
+}
+
+int vcg_pack_conv_in_gate_bf16(const void* w_hwio, int32_t cin, int32_t kh, int32_t kw, int32_t cout, void* out, hipStream_t stream) {
+    VCG_CHECK_PTR(w_hwio);
+    VCG_CHECK_PTR(out);
+    if (!in_gate_supported(cin, kh, kw, cout)) return VCG_E_UNSUPPORTED;
+    const int ng = ceil_div(kw, 4), total = (cout >> 6) * (cin / 3) * kh * ng * 64 * 2;
+    pack_in_gate_kernel<<<(total + 255) / 256, 256, 0, stream>>>((const float*)w_hwio, (uint4*)out, cin, cout, kh, kw, ng);
+    VCG_LAUNCH_CHECK();
+    return VCG_OK;
+}
+
+int vcg_conv_in_gate_bf16_fwd(const vcg_conv_desc* d, const void* u, const void* wfrag, const void* bias, const void* m, void* y, hipStream_t stream) {
+    VCG_CHECK_PTR(d);
+    VCG_CHECK_PTR(u);
+    VCG_CHECK_PTR(wfrag);
+    VCG_CHECK_PTR(m);
+    VCG_CHECK_PTR(y);
+    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->oh != d->h || d->ow != d->w) return VCG_E_SHAPE;
+    if (!in_gate_supported(d->cin, d->kh, d->kw, d->cout) || d->stride != 1 || d->pad_top != d->kh / 2 || d->pad_left != d->kw / 2)
+        return VCG_E_UNSUPPORTED;
+    if (y == m) return VCG_E_UNSUPPORTED;                 // the residual block still adds the ungated m
+    if ((long)d->n * ceil_div(d->w, TC) * ceil_div(d->h, TR) > 0x7FFFFFFFl) return VCG_E_UNSUPPORTED;
+    I9Params p;
+    p.chsum = nullptr;
+    p.x = (const float*)u;
+    p.w = (const uint4*)wfrag;
+    p.bias = (const float*)bias;
+    p.alpha = nullptr;
+    p.xcd_group = 0;
+    p.slope = 1.f;
+    p.y = (__bf16*)y;
+    p.z = nullptr;
+    p.mask = (const __bf16*)m;
+    p.mask_slope = 0.f;
+    p.n = d->n; p.h = d->h; p.w_ = d->w; p.cout = d->cout;
+    p.oh = d->oh; p.ow = d->ow; p.pad_top = d->pad_top; p.pad_left = d->pad_left;
+    p.tiles_x = ceil_div(d->ow, TC);
+    p.tiles_y = ceil_div(d->oh, TR);
+    p.total = p.n * p.tiles_x * p.tiles_y;
+    if (d->kh == 3) return d->cin == 3 ? launch_conv3ch<3, 1, 1, 1, true>(p, stream) : launch_conv3ch<3, 1, 1, 2, true>(p, stream);
+    return d->cin == 3 ? launch_conv3ch<5, 2, 1, 1, true>(p, stream) : launch_conv3ch<5, 2, 1, 2, true>(p, stream);
 }
 
 int vcg_conv9x9_from3_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* wfrag, const void* bias, const void* prelu_alpha,

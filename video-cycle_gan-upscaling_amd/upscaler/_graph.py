@@ -550,7 +550,18 @@ def make_upscaler_attention(output_image_shape, kernel_size=5, filters=64, upsca
         scale = 2 ** (index + 1)
         model = upsampling_block_attention(model, upscaler_input, scale, kernel_size, 128, name="upscaling/" + str(index) + "/block")
     model = conv2d(model, 3, 9, 1, "same", activation="tanh", name="final/conv")
-    return build_model(upscaler_input, model, name="upscaler_attention", seed=seed)
+    net = build_model(upscaler_input, model, name="upscaler_attention", seed=seed)
+    # what the bf16 inference engine recognises the topology by (not the name string), and its entry point
+    net.attention_generator = {"kernel_size": kernel_size, "filters": filters, "upscale_factor": upscale_factor, "res_block_num": res_block_num,
+                               "norm": norm, "channels": output_image_shape[2]}
+    net.to_inference_bf16 = lambda: _attention_bf16(net)
+    return net
+
+
+def _attention_bf16(net):
+    """inference engine on the bf16-storage kernels (BN folded, one hipGraph per input shape): ``_infer.Bf16AttentionGenerator``"""
+    from ._infer import Bf16AttentionGenerator
+    return Bf16AttentionGenerator(net)
 
 
 def make_generator_cyclegan(output_image_shape, filters=64, n_downsample=2, res_block_num=9, upscale_factor=1, norm="instance",

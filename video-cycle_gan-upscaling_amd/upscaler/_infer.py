@@ -35,6 +35,8 @@ BN_EPS = 1e-3          # keras.layers.BatchNormalization default (SURVEY.md Appe
 
 
 class Bf16Generator:
+    TAIL_CHANNELS = 256        # channels of the up-sampling stages' outputs (model.py:288): what the 4 GiB rule of _tail_chunk counts
+
     def __init__(self, model):
         from .model import UpscalerOrig
         if not isinstance(model, UpscalerOrig):
@@ -139,7 +141,7 @@ class Bf16Generator:
         if self.legacy:
             return n
         f = 2 ** len(self.ups)
-        per = f * f * h * w * 256 * 2
+        per = f * f * h * w * self.TAIL_CHANNELS * 2
         ch = max(1, min(n, 0xFFFFFFE0 // per))
         launches = -(-n // ch)
         return -(-n // launches)                 # the same number of launches, frames spread evenly (32 -> 16 + 16, not 31 + 1)
@@ -248,3 +250,161 @@ class Bf16Generator:
             y = self.replay(xb)
             outs.append(E.to_nhwc(rt, y).cpu().numpy())
         return np.concatenate(outs, 0)
+
+
+class Bf16AttentionGenerator(Bf16Generator):
+    """The same engine for ``make_upscaler_attention`` models (upscaling/upscaler/model.py:299-328; train_gan3.py's default
+    ``-gm resnet-att``), filters 64 on RGB frames, BatchNormalization, kernel_size 3 or 5, upscale_factor 2 or 4, any res_block_num:
+
+        initial/conv 9x9 3->64 + PReLU                          vcg_conv9x9_from3_bf16_fwd
+        res blocks: sigmoid(conv(frames)) * m                   vcg_conv_in_gate_bf16_fwd (cin 3; the attention tensor is never stored)
+                    conv + BN + PReLU, conv + BN + Add(m)       vcg_conv2d_bf16_fwd, the Add takes the UNGATED block input (model.py:48)
+        after_res conv + BN + Add(long skip)                    vcg_conv2d_bf16_fwd
+        up-sampling block i (scale s = 2**(i+1)):
+            u = [nearest, bilinear](frames, s/2)                vcg_resize2d / vcg_copy_channels, fp32 NCHW, 6 channels (data only)
+            sigmoid(conv(u)) * m                                vcg_conv_in_gate_bf16_fwd (cin 6)
+            ConvT k s2 -> 128 + LeakyReLU(0.2)                  vcg_conv_transpose2d_nhwc_bf16_fwd
+            + ConvT(s+1, strides s)(atanh(0.99999 frames))      vcg_input_convt_add_bf16, in place
+        final/conv 9x9 128->3 + tanh                            vcg_conv9x9_to3_bf16_fwd (cin 128)
+
+    3 launches per residual block; _fold, _pack, capture / replay / predict and the 4 GiB chunking of the tail are Bf16Generator's."""
+    TAIL_CHANNELS = 128
+    SERVED = "bf16 inference of make_upscaler_attention is instantiated for filters=64 on 3-channel (RGB) frames, norm='batch', " \
+             "kernel_size 3 or 5 and upscale_factor 2 or 4 (any res_block_num); use model.predict for other shapes"
+
+    def __init__(self, model):
+        cfg = getattr(model, "attention_generator", None)
+        if cfg is None or not hasattr(model, "graph"):
+            raise TypeError("Bf16AttentionGenerator serves make_upscaler_attention models")
+        if cfg["filters"] != 64 or cfg["channels"] != 3 or cfg["norm"] != "batch" or cfg["kernel_size"] not in (3, 5) \
+                or cfg["upscale_factor"] not in (2, 4):
+            raise NotImplementedError(self.SERVED)
+        self.k = cfg["kernel_size"]
+        self.res_block_num, self.upscale_times = cfg["res_block_num"], {2: 1, 4: 2}[cfg["upscale_factor"]]
+        self.legacy = False
+        self.instance = False
+        self.model = model
+        self.rt = model.rt
+        self.layers = {l.name: l for l in model.layers}
+        self._graphs = {}
+        self._bufs = {}
+        self.refresh()
+
+    @staticmethod
+    def _generic(conv, transpose):
+        """every transposed convolution (64 -> 128, 128 -> 128) and the 5x5 trunk run on the generic kernels"""
+        return not transpose or conv.k != 3
+
+    def _pack_gate(self, conv):
+        rt = self.rt
+        nbytes = rt.lib.vcg_conv_in_gate_bf16_wfrag_bytes(conv.cin, conv.k, conv.k, conv.cout)
+        if nbytes == 0:
+            raise NotImplementedError(self.SERVED)
+        out = torch.empty(nbytes, dtype=torch.uint8, device=rt.device)
+        L.check(rt.lib.vcg_pack_conv_in_gate_bf16(conv.ps[conv.name + "/kernel"].data_ptr(), conv.cin, conv.k, conv.k, conv.cout, out.data_ptr(),
+                                                  rt.stream), "vcg_pack_conv_in_gate_bf16")
+        return out, conv.ps[conv.name + "/bias"]
+
+    def refresh(self):
+        """(re)derive the packed bf16 weights and the folded BatchNormalization vectors from the model's parameters"""
+        rt, ly = self.rt, self.layers
+        ps = self.model.ps
+        self.trunk = []
+        for i in range(self.res_block_num):
+            n = "res_block/%d" % i
+            c1, n1, c2, n2 = ly[n + "/conv_pre"], ly[n + "/batch_norm_pre"], ly[n + "/conv_post"], ly[n + "/batch_norm_post"]
+            s1, h1 = self._fold(c1, n1)
+            s2, h2 = self._fold(c2, n2)
+            self.trunk.append((self._pack_gate(ly[n + "/attention"]), self._pack(c1, 1), s1, h1, ps[n1.prelu_name + "/alpha"],
+                               self._pack(c2, 1), s2, h2))
+        ca = ly["after_res/conv"]
+        sp, hp = self._fold(ca, ly["after_res/batch_norm"])
+        self.prefinal = (self._pack(ca, 1), sp, hp)
+        self.ups = []
+        for i in range(self.upscale_times):
+            n = "upscaling/%d/block" % i
+            up, ta = ly[n + "/conv_transp"], ly[n + "/to_add_input_conv_transp"]
+            self.ups.append((self._pack_gate(ly[n + "/attention"]), self._pack(up, 0), ps[up.name + "/bias"], float(up.alpha), up.cin, up.cout,
+                             ps[ta.name + "/kernel"], ps[ta.name + "/bias"]))
+        cf = ly["final/conv"]
+        wf = torch.empty(rt.lib.vcg_conv9x9_to3_bf16_wfrag_bytes(cf.cin), dtype=torch.uint8, device=rt.device)
+        L.check(rt.lib.vcg_pack_conv9x9_to3_bf16(ps[cf.name + "/kernel"].data_ptr(), cf.cin, wf.data_ptr(), rt.stream), "vcg_pack_conv9x9_to3_bf16")
+        self.final = (wf, ps[cf.name + "/bias"], cf.cin)
+        c0 = ly["initial/conv"]
+        w0 = torch.empty(L.FIRST9X9_WFRAG_BYTES, dtype=torch.uint8, device=rt.device)
+        L.check(rt.lib.vcg_pack_first9x9_bf16(ps[c0.name + "/kernel"].data_ptr(), w0.data_ptr(), rt.stream), "vcg_pack_first9x9_bf16")
+        self.first = (w0, ps[c0.name + "/bias"], ps["initial/prelu/alpha"])
+        self._graphs.clear()          # recorded graphs hold the old parameter buffers
+
+    def _buffers(self, n, h, w):
+        key = (n, h, w)
+        if key not in self._bufs:
+            dev = self.rt.device
+            bf = lambda nn, c, hh, ww: torch.empty(nn, hh, ww, c, dtype=torch.bfloat16, device=dev)
+            ch = self._tail_chunk(n, h, w)
+            f = 2 ** len(self.ups)
+            stages = []
+            for s, up in enumerate(self.ups):
+                r, cin, cout = 2 ** s, up[4], up[5]
+                stages.append({"u": torch.empty(n, 6, r * h, r * w, dtype=torch.float32, device=dev),      # [nearest, bilinear] of the frames
+                               "t": torch.empty(n, 3, r * h, r * w, dtype=torch.float32, device=dev) if r > 1 else None,
+                               "g": bf(ch, cin, r * h, r * w), "y": bf(ch, cout, 2 * r * h, 2 * r * w)})
+            self._bufs[key] = {"skip": bf(n, 64, h, w), "a": bf(n, 64, h, w), "b": bf(n, 64, h, w), "c": bf(n, 64, h, w), "g": bf(n, 64, h, w),
+                               "stages": stages, "chunk": ch,
+                               "y": torch.empty(n, 3, f * h, f * w, dtype=torch.float32, device=dev)}
+        return self._bufs[key]
+
+    def _gate(self, gate, u, cin, m, y, n, h, w):
+        (wg, bg), k, rt = gate, self.k, self.rt
+        d = L.ConvDesc(n, cin, h, w, m.shape[3], h, w, k, k, 1, k // 2, k // 2)
+        L.check(rt.lib.vcg_conv_in_gate_bf16_fwd(ctypes.byref(d), u.data_ptr(), wg.data_ptr(), bg.data_ptr(), m.data_ptr(), y.data_ptr(), rt.stream),
+                "vcg_conv_in_gate_bf16_fwd")
+
+    def forward(self, x):
+        """x: device fp32 NCHW [n,3,h,w] in [-1,1] -> device fp32 NCHW [n,3,f*h,f*w] (f = upscale_factor; buffer owned by the engine)"""
+        rt = self.rt
+        n, _, h, w = x.shape
+        B = self._buffers(n, h, w)
+        w0, b0, a0 = self.first
+        d0 = L.ConvDesc(n, 3, h, w, 64, h, w, 9, 9, 1, 4, 4)
+        L.check(rt.lib.vcg_conv9x9_from3_bf16_fwd(ctypes.byref(d0), x.data_ptr(), w0.data_ptr(), b0.data_ptr(), a0.data_ptr(),
+                                                  B["skip"].data_ptr(), rt.stream), "vcg_conv9x9_from3_bf16_fwd")
+        cur = B["skip"]                     # block input; outputs ping-pong between "a" and "c", "skip" is never overwritten
+        for (gate, w1, s1, h1, al, w2, s2, h2) in self.trunk:
+            out = B["a"] if cur is not B["a"] else B["c"]
+            self._gate(gate, x, 3, cur, B["g"], n, h, w)
+            self._conv(B["g"], w1, B["b"], s1, h1, L.ACT_PRELU, al, None, n, h, w)
+            self._conv(B["b"], w2, out, s2, h2, L.ACT_NONE, None, cur, n, h, w)          # Add of the ungated block input
+            cur = out
+        wp, sp, hp = self.prefinal
+        out = B["a"] if cur is not B["a"] else B["c"]
+        self._conv(cur, wp, out, sp, hp, L.ACT_NONE, None, B["skip"], n, h, w)
+        # the gates' inputs: data derived from the frames alone, for the whole batch
+        for s, st in enumerate(B["stages"]):
+            r, hw = 2 ** s, h * w
+            for off, bil in ((0, 0), (3, 1)):
+                src = x
+                if r > 1:
+                    L.check(rt.lib.vcg_resize2d(x.data_ptr(), st["t"].data_ptr(), n * 3, h, w, r, bil, rt.stream), "vcg_resize2d")
+                    src = st["t"]
+                L.check(rt.lib.vcg_copy_channels(src.data_ptr(), st["u"].data_ptr(), n, 3, 0, 6, off, 3, r * r * hw, rt.stream), "vcg_copy_channels")
+        wf, bf_, cfin = self.final
+        k, crop = self.k, max(self.k - 2, 0) // 2           # TF-SAME crop of Conv2DTranspose(k, strides 2): k3 (0, 1), k5 (1, 2)
+        y, ch = B["y"], B["chunk"]
+        for i in range(0, n, ch):
+            c = min(ch, n - i)
+            src, hh, ww = out[i:i + c], h, w
+            for s, ((gate, wt, bt, slope, cin, cout, wa, ba), st) in enumerate(zip(self.ups, B["stages"])):
+                scale = 2 ** (s + 1)
+                self._gate(gate, st["u"][i:i + c], 6, src, st["g"], c, hh, ww)
+                dt = L.ConvDesc(c, cin, hh, ww, cout, 2 * hh, 2 * ww, k, k, 2, crop, crop)
+                L.check(rt.lib.vcg_conv_transpose2d_nhwc_bf16_fwd(ctypes.byref(dt), st["g"].data_ptr(), wt.data_ptr(), bt.data_ptr(), L.ACT_LRELU,
+                                                                  slope, st["y"].data_ptr(), rt.stream), "vcg_conv_transpose2d_nhwc_bf16_fwd")
+                da = L.ConvDesc(c, 3, h, w, cout, scale * h, scale * w, scale + 1, scale + 1, scale, 0, 0)
+                L.check(rt.lib.vcg_input_convt_add_bf16(ctypes.byref(da), x[i:i + c].data_ptr(), wa.data_ptr(), ba.data_ptr(), st["y"].data_ptr(),
+                                                        rt.stream), "vcg_input_convt_add_bf16")
+                src, hh, ww = st["y"], 2 * hh, 2 * ww
+            df = L.ConvDesc(c, cfin, hh, ww, 3, hh, ww, 9, 9, 1, 4, 4)
+            L.check(rt.lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, y[i:i + c].data_ptr(),
+                                                    rt.stream), "vcg_conv9x9_to3_bf16_fwd")
+        return y
