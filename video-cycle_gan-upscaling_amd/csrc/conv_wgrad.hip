@@ -17,6 +17,10 @@
 // go to the workspace and a second kernel sums them in a fixed order (deterministic) and scatters
 // into the Keras kernel layout.  When A = dy the per-channel sums of the staged A tiles give the
 // bias gradient for free (db partials ride along in the same workspace).
+// The big layouts run one wave per SIMD, so every instruction of the tile loop that is not an MFMA
+// is exposed: staging addresses are decoded once per kernel (a thread keeps its pixel / halo row and
+// walks channels), the tile coordinates are carried, and the bias gradient's chain of LDS reads and
+// adds rides inside the MFMA loop, read one pair of k-steps ahead.
 #include "vcg_common.hpp"
 
 namespace {
@@ -57,18 +61,88 @@ struct WgCfg {
     static constexpr int BPS = round_to(BH * BRS, T % 32);
     static constexpr int A_ELEMS = 64 * TH * 32;
     static constexpr int B_ELEMS = JCMAX * BH * BW;
-    static constexpr int A_PT = (A_ELEMS + NT - 1) / NT;
-    // B staging: thread = (row group, column) over whole 32-column segments of the halo rows -- (channel, row)
-    // come from one small division per ROW instead of three per element -- plus a flat pass for the BW % 32
-    // remaining halo columns
+    // A staging: element e = tid + i * NT of the [64][TH][32] tile.  NT is a multiple of the 32 * TH pixels of a channel, so a
+    // thread keeps its pixel for every i and only its channel advances, by MS
+    static constexpr int MS = NT / (32 * TH);
+    static constexpr int A_PT = A_ELEMS / NT;
+    static_assert(NT % (32 * TH) == 0 && A_ELEMS % NT == 0, "a thread's A elements must share one pixel");
+    // B staging: thread = (row group, column) over whole 32-column segments of the halo rows, plus a second family of
+    // passes for the BW % 32 remaining halo columns (REMP lanes per row); BStage decodes both
     static constexpr int RG = NT / 32;
     static constexpr int ROWS = JCMAX * BH;
     static constexpr int QSEG = BW / 32, REM = BW % 32;
     static constexpr int RPT = (ROWS + RG - 1) / RG;
-    static constexpr int HPT = (ROWS * REM + NT - 1) / NT;
-    static constexpr int REMD = REM > 0 ? REM : 1;       // divisor of the remainder pass (which is empty when BW is a multiple of 32)
+    static constexpr int REMP = REM <= 1 ? 1 : REM <= 2 ? 2 : REM <= 4 ? 4 : 8;
+    static_assert(REM <= 8, "remainder columns: at most 8 (KW <= 9)");
+    static constexpr int RGH = NT / REMP;
+    static constexpr int HPT = REM > 0 ? (ROWS + RGH - 1) / RGH : 0;
     static constexpr int B_PT = RPT * QSEG + HPT;
     static constexpr size_t LDS_BYTES = ((size_t)64 * AST + (size_t)JCMAX * BPS + 64) * sizeof(float);
+};
+
+constexpr int wg_gcd(int a, int b) { return b == 0 ? a : wg_gcd(b, a % b); }
+
+// One family of B staging passes.  The thread stages column col (+ 32 per segment, NQ segments) of the halo rows
+// g + i * RGX (i < NP) out of the ROWS = JCMAX * BH rows of the tile.  (channel, halo row) of a row come from a division,
+// but row i + P is row i moved by JS whole channels: P decoded rows (kept for the kernel's lifetime, P <= 5) serve every
+// pass, and per tile ONE validity select per decoded row and segment covers all the channels the thread walks.  A load
+// is then "offset += channel stride": no multiplication, no per-load predicate, no exec-mask region.  Channels past the
+// block's last one are beyond the descriptor's range and read as 0.
+template <int RGX, int NP, int NQ, int BH, int ROWS, int BPS, int BRS>
+struct BStage {
+    static constexpr int P0 = BH / wg_gcd(RGX, BH), JS = P0 * RGX / BH;
+    static constexpr int P = NP <= 0 ? 1 : (P0 < NP ? P0 : NP);      // decoded rows in use
+    int gs[P], ls[P], rr[P];   // offset inside the image's channel block, LDS offset, halo row
+    int g, col;
+    bool cval;                 // the thread has a column at all (remainder passes: REM of REMP lanes)
+    __device__ __forceinline__ void init(int g_, int col_, bool cval_, int bh, int bw) {
+        g = g_; col = col_; cval = cval_;
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+            const int row = g + k * RGX;
+            const int jc = row / BH, r = row % BH;
+            gs[k] = (jc * bh + r) * bw + col;
+            ls[k] = jc * BPS + r * BRS + col;
+            rr[k] = r;
+        }
+    }
+    // (by0, bx0): the tile's corner in the image (negative in the padding), tb = by0 * bw + bx0, cs = JS channels in bytes
+    __device__ __forceinline__ void load(float* rb, vcg_rsrc rB, int by0, int bx0, int tb, int bh, int bw, unsigned cs) const {
+        unsigned vo[P][NQ], st[P][NQ];
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+            const bool rok = cval && (unsigned)(by0 + rr[k]) < (unsigned)bh;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const bool ok = rok && (unsigned)(bx0 + col + q * 32) < (unsigned)bw;
+                vo[k][q] = ok ? 4u * (unsigned)(gs[k] + tb + q * 32) : VCG_OOB;
+                st[k][q] = ok ? cs : 0u;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int k = i % P;
+            // only the last passes can run past the tile's rows (compile-time known which)
+            const bool tail = (RGX - 1) + i * RGX >= ROWS;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                unsigned off = vo[k][q];
+                if (tail) off = (g + i * RGX < ROWS) ? off : VCG_OOB;
+                rb[i * NQ + q] = buf_load(rB, off);
+                vo[k][q] += st[k][q];
+            }
+        }
+    }
+    __device__ __forceinline__ void store(float* s_b, const float* rb) const {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int k = i % P, u = i / P;
+            if (cval && g + i * RGX < ROWS) {
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) s_b[ls[k] + u * JS * BPS + q * 32] = rb[i * NQ + q];
+            }
+        }
+    }
 };
 
 template <int S, int NW, int NJ, int MW, int TH, int KH, int KW>
@@ -111,113 +185,115 @@ __global__ __launch_bounds__(64 * NW, (MW * NJ * 16 > 100 ? 1 : 2)) void wgrad_k
         for (int i = 0; i < NJ; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][i][r] = 0.f;
+    // bias gradient (A = dy): wave 0 sums the staged A tile, lane = channel row (odd row stride: conflict-free), pixel after
+    // pixel and tile after tile in ONE fixed chain per channel -- the order is part of the result (db of a bias in front of a
+    // normalisation is rounding noise, and Adam turns noise of any size into a step of lr).  The chain rides inside the MFMA
+    // loop: four values per pair of k-steps, read one pair ahead and added between the pair's two MFMA runs, so that neither
+    // the LDS latency nor the dependent adds stand in front of the matrix pipe.
+    const bool do_db = p.dbpart != nullptr && jb == 0 && __builtin_amdgcn_readfirstlane(wv) == 0;   // wave-uniform: scalar branches
     float dbacc = 0.f;
-    const bool do_db = p.dbpart != nullptr && jb == 0 && wv == 0;
+    const float* dbrow = s_a + lane * C::AST;
 
     const int t_begin = slab * p.tiles_per_slab;
     const int t_end = min(t_begin + p.tiles_per_slab, p.tiles_total);
 
+    // ---- staging addresses, decoded once.  A: the thread's pixel (ar, ac) of the tile and first channel mt; the
+    // channel advances by MS per load.  B: see BStage.
+    const int ac = tid & 31, ar = (tid >> 5) % TH, mt = tid / (32 * TH);
+    const int a_plane = p.ah * p.aw, b_plane = p.bh * p.bw;
+    const int a_gs = ((m0 + mt) * p.ah + ar) * p.aw + ac;
+    const unsigned a_cs = 4u * (unsigned)(C::MS * a_plane);
+    const size_t a_img = (size_t)p.mtot * a_plane, b_img = (size_t)p.jctot * b_plane;
+    const float* b_blk = p.B + (size_t)jc0 * b_plane;
+    const unsigned b_bytes = (unsigned)(jc_here * b_plane) * 4u;      // channels past the block's last one read as 0
+    using BMain = BStage<C::RG, C::RPT, C::QSEG, C::BH, C::ROWS, C::BPS, C::BRS>;
+    using BRem = BStage<C::RGH, C::HPT, 1, C::BH, C::ROWS, C::BPS, C::BRS>;
+    BMain bmain;
+    BRem brem;
+    bmain.init(tid >> 5, tid & 31, true, p.bh, p.bw);
+    brem.init(tid / C::REMP, C::QSEG * 32 + tid % C::REMP, tid % C::REMP < C::REM, p.bh, p.bw);
+
+    // coordinates of the next tile to load, carried from tile to tile (wave-uniform)
+    int ltx, lty, ln;
+    {
+        int q = t_begin;
+        ltx = q % p.tiles_x; q /= p.tiles_x;
+        lty = q % p.tiles_y; ln = q / p.tiles_y;
+    }
+
     float ra[C::A_PT], rb[C::B_PT];
-    auto load_tile = [&](int tile) {
-        int q = tile;
-        const int tx = q % p.tiles_x; q /= p.tiles_x;
-        const int ty = q % p.tiles_y; q /= p.tiles_y;
-        const int n = q;
-        const int ax0 = tx * 32, ay0 = ty * TH;
+    auto load_tile = [&]() {
+        const int ax0 = ltx * 32, ay0 = lty * TH;
         // range-checked buffer loads (vcg_common.hpp): the validity select sits on the ADDRESS, nothing depends on the
-        // loaded data until store_tile -- the prefetch really flies under the MFMA loop
-        const vcg_rsrc rA = make_rsrc(p.A + (size_t)n * p.mtot * p.ah * p.aw, (size_t)p.mtot * p.ah * p.aw * sizeof(float));
+        // loaded data until store_tile -- the prefetch really flies under the MFMA loop.  One select per tile covers the
+        // ragged right / bottom edge for every channel (an invalid thread's offset stays VCG_OOB: its stride is 0);
+        // channels past mtot lie beyond the descriptor's range.
+        const vcg_rsrc rA = make_rsrc(p.A + (size_t)ln * a_img, a_img * sizeof(float));
+        const bool aok = ay0 + ar < p.ah && ax0 + ac < p.aw;
+        unsigned avo = aok ? 4u * (unsigned)(a_gs + ay0 * p.aw + ax0) : VCG_OOB;
+        const unsigned ast = aok ? a_cs : 0u;
 #pragma unroll
         for (int i = 0; i < C::A_PT; ++i) {
-            const int e = tid + i * C::NT;
-            const int c = e & 31, r = (e >> 5) % TH, m = e / (32 * TH);
-            const int ay = ay0 + r, ax = ax0 + c;
-            const bool ok = e < C::A_ELEMS && m0 + m < p.mtot && ay < p.ah && ax < p.aw;
-            ra[i] = buf_load(rA, ok ? 4u * (unsigned)(((m0 + m) * p.ah + ay) * p.aw + ax) : VCG_OOB);
+            ra[i] = buf_load(rA, avo);
+            avo += ast;
         }
-        const vcg_rsrc rB = make_rsrc(p.B + ((size_t)n * p.jctot + jc0) * p.bh * p.bw, (size_t)(p.jctot - jc0) * p.bh * p.bw * sizeof(float));
+        const vcg_rsrc rB = make_rsrc(b_blk + (size_t)ln * b_img, b_bytes);
         const int by0 = ay0 * S - p.pt, bx0 = ax0 * S - p.pl;
-        const int c32 = tid & 31, rg = tid >> 5;
-#pragma unroll
-        for (int i = 0; i < C::RPT; ++i) {
-            const int row = rg + i * C::RG;
-            const int jc = row / C::BH, r = row % C::BH;
-            const int by = by0 + r;
-            const bool rok = row < C::ROWS && jc < jc_here && by >= 0 && by < p.bh;
-            const int rbase = (jc * p.bh + by) * p.bw + bx0;
-#pragma unroll
-            for (int q = 0; q < C::QSEG; ++q) {
-                const int bx = bx0 + q * 32 + c32;
-                const bool ok = rok && bx >= 0 && bx < p.bw;
-                rb[i * C::QSEG + q] = buf_load(rB, ok ? 4u * (unsigned)(rbase + q * 32 + c32) : VCG_OOB);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < C::HPT; ++i) {
-            const int e = tid + i * C::NT;
-            const int row = e / C::REMD, c = C::QSEG * 32 + e % C::REMD;
-            const int jc = row / C::BH, r = row % C::BH;
-            const int by = by0 + r, bx = bx0 + c;
-            const bool ok = row < C::ROWS && jc < jc_here && by >= 0 && by < p.bh && bx >= 0 && bx < p.bw;
-            rb[C::RPT * C::QSEG + i] = buf_load(rB, ok ? 4u * (unsigned)((jc * p.bh + by) * p.bw + bx) : VCG_OOB);
+        const int tb = by0 * p.bw + bx0;
+        bmain.load(rb, rB, by0, bx0, tb, p.bh, p.bw, 4u * (unsigned)(BMain::JS * b_plane));
+        brem.load(rb + C::RPT * C::QSEG, rB, by0, bx0, tb, p.bh, p.bw, 4u * (unsigned)(BRem::JS * b_plane));
+        if (++ltx == p.tiles_x) {
+            ltx = 0;
+            if (++lty == p.tiles_y) { lty = 0; ++ln; }
         }
     };
     auto store_tile = [&]() {
 #pragma unroll
-        for (int i = 0; i < C::A_PT; ++i) {
-            const int e = tid + i * C::NT;
-            if (e < C::A_ELEMS) {
-                const int c = e & 31, r = (e >> 5) % TH, m = e / (32 * TH);
-                s_a[m * C::AST + r * 32 + c] = ra[i];
-            }
-        }
-        const int c32 = tid & 31, rg = tid >> 5;
-#pragma unroll
-        for (int i = 0; i < C::RPT; ++i) {
-            const int row = rg + i * C::RG;
-            if (row < C::ROWS) {
-                const int jc = row / C::BH, r = row % C::BH;
-#pragma unroll
-                for (int q = 0; q < C::QSEG; ++q) s_b[jc * C::BPS + r * C::BRS + q * 32 + c32] = rb[i * C::QSEG + q];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < C::HPT; ++i) {
-            const int e = tid + i * C::NT;
-            const int row = e / C::REMD, c = C::QSEG * 32 + e % C::REMD;
-            if (row < C::ROWS) {
-                const int jc = row / C::BH, r = row % C::BH;
-                s_b[jc * C::BPS + r * C::BRS + c] = rb[C::RPT * C::QSEG + i];
-            }
-        }
+        for (int i = 0; i < C::A_PT; ++i) s_a[(mt + i * C::MS) * C::AST + ar * 32 + ac] = ra[i];
+        bmain.store(s_b, rb);
+        brem.store(s_b, rb + C::RPT * C::QSEG);
     };
 
-    if (t_begin < t_end) load_tile(t_begin);
+    if (t_begin < t_end) load_tile();
     for (int tile = t_begin; tile < t_end; ++tile) {
         __syncthreads();  // previous tile fully consumed
         store_tile();
         __syncthreads();
-        if (tile + 1 < t_end) load_tile(tile + 1);  // in flight during the MFMA loop
+        if (tile + 1 < t_end) load_tile();  // in flight during the MFMA loop
+        float dv[4];
         if (do_db) {
-            // bias gradient: lane = channel row of the staged dy tile (odd row stride: conflict-free)
-            const float* row = s_a + lane * C::AST;
 #pragma unroll
-            for (int i = 0; i < TH * 32; ++i) dbacc += row[i];
+            for (int e = 0; e < 4; ++e) dv[e] = dbrow[e];
         }
+        // pairs of k-steps (the MFMA order -- r, st, i, m -- is what it always was)
 #pragma unroll
-        for (int r = 0; r < TH; ++r) {
+        for (int g = 0; g < TH * 8; ++g) {
+            const int r = g / 8, st = 2 * (g % 8);
+            float av[2][MW], bv[2][NJ];
 #pragma unroll
-            for (int st = 0; st < 16; ++st) {
-                float av[MW];
+            for (int h = 0; h < 2; ++h) {
 #pragma unroll
-                for (int m = 0; m < MW; ++m) av[m] = ap0[m * 32 * C::AST + r * 32 + 2 * st];
+                for (int m = 0; m < MW; ++m) av[h][m] = ap0[m * 32 * C::AST + r * 32 + 2 * (st + h)];
 #pragma unroll
-                for (int i = 0; i < NJ; ++i) {
-                    const float bv = s_b[boff[i] + (r * S) * C::BRS + 2 * st * S];
+                for (int i = 0; i < NJ; ++i) bv[h][i] = s_b[boff[i] + (r * S) * C::BRS + 2 * (st + h) * S];
+            }
 #pragma unroll
-                    for (int m = 0; m < MW; ++m) acc[m][i] = mfma32(av[m], bv, acc[m][i]);
+            for (int i = 0; i < NJ; ++i)
+#pragma unroll
+                for (int m = 0; m < MW; ++m) acc[m][i] = mfma32(av[0][m], bv[0][i], acc[m][i]);
+            if (do_db) {
+                // pixels 4g .. 4g+3 of the channel row, then the next pair's four on their way
+#pragma unroll
+                for (int e = 0; e < 4; ++e) dbacc += dv[e];
+                if (g + 1 < TH * 8) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dv[e] = dbrow[4 * (g + 1) + e];
                 }
             }
+#pragma unroll
+            for (int i = 0; i < NJ; ++i)
+#pragma unroll
+                for (int m = 0; m < MW; ++m) acc[m][i] = mfma32(av[1][m], bv[1][i], acc[m][i]);
         }
     }
 
@@ -241,9 +317,30 @@ struct ReduceParams {
     float* db;
     int slabs, m_pad, j_pad, mtot, jctot, jc, jbw, T;
     int ts, sm, sj;  // dw[tap*ts + m*sm + jc*sj]
+    int dw_blocks;   // blocks of the dw part; the db blocks follow
 };
 
+// blocks [0, dw_blocks): dw; blocks behind them (only when db is wanted): db[m] = sum over slabs of dbpart[slab][m],
+// 256 threads = 64 channels x 4 slab groups.  Both in a fixed summation order (deterministic).
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const ReduceParams p) {
+    if ((int)blockIdx.x >= p.dw_blocks) {
+        __shared__ float red[4][64];
+        const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
+        const int m = ((int)blockIdx.x - p.dw_blocks) * 64 + c;
+        float s4[4] = {0.f, 0.f, 0.f, 0.f};
+        if (m < p.mtot) {
+            int k = g;
+            for (; k + 12 < p.slabs; k += 16) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) s4[u] += p.dbpart[(size_t)(k + 4 * u) * p.m_pad + m];
+            }
+            for (; k < p.slabs; k += 4) s4[0] += p.dbpart[(size_t)k * p.m_pad + m];
+        }
+        red[g][c] = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+        __syncthreads();
+        if (g == 0 && m < p.mtot) p.db[m] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+        return;
+    }
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t total = (size_t)p.m_pad * p.j_pad;
     if (idx >= total) return;
@@ -266,25 +363,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const ReduceParams p)
         if (k + u < p.slabs) s8[u] += src[(size_t)(k + u) * total];
     const float s = ((s8[0] + s8[1]) + (s8[2] + s8[3])) + ((s8[4] + s8[5]) + (s8[6] + s8[7]));
     p.dw[(size_t)t * p.ts + (size_t)m * p.sm + (size_t)jc * p.sj] = s;
-}
-
-// db[m] = sum over slabs of dbpart[slab][m]: 256 threads = 64 channels x 4 slab groups, fixed order
-__global__ __launch_bounds__(256) void wgrad_db_reduce_kernel(const float* dbpart, float* db, int slabs, int m_pad, int mtot) {
-    __shared__ float red[4][64];
-    const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int m = blockIdx.x * 64 + c;
-    float s4[4] = {0.f, 0.f, 0.f, 0.f};
-    if (m < mtot) {
-        int k = g;
-        for (; k + 12 < slabs; k += 16) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) s4[u] += dbpart[(size_t)(k + 4 * u) * m_pad + m];
-        }
-        for (; k < slabs; k += 4) s4[0] += dbpart[(size_t)k * m_pad + m];
-    }
-    red[g][c] = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-    __syncthreads();
-    if (g == 0 && m < mtot) db[m] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
 }
 
 struct Plan {
@@ -368,6 +446,10 @@ int vcg_internal_wgrad(const float* A, const float* B, float* dw, float* db, int
     Plan pl = make_plan(n, mtot, ah, aw, jctot, kh, kw, S);
     if (!pl.ok) return VCG_E_UNSUPPORTED;
     if (ws == nullptr || ws_bytes < pl.ws_bytes) return VCG_E_WORKSPACE;
+    // staging offsets are 32-bit and a thread walks its whole channel block, the padding channels behind the last real one included
+    const size_t jc_cap = (size_t)((pl.MW == 2 ? pl.NW : pl.NW / 2) * pl.NJ * 32 / (kh * kw));
+    if ((size_t)pl.m_pad * ah * aw * sizeof(float) >= 0xFFFFFFE0u || (jc_cap + 1) * bh * bw * sizeof(float) >= 0xFFFFFFE0u)
+        return VCG_E_UNSUPPORTED;
     WgradParams p{};
     p.A = A; p.B = B; p.part = (float*)ws;
     p.dbpart = db ? (float*)((char*)ws + pl.ws_part_bytes) : nullptr;
@@ -405,12 +487,9 @@ int vcg_internal_wgrad(const float* A, const float* B, float* dw, float* db, int
     r.mtot = mtot; r.jctot = jctot; r.jc = pl.jc; r.jbw = (pl.MW == 2 ? pl.NW : pl.NW / 2) * pl.NJ * 32; r.T = kh * kw;
     r.ts = ts; r.sm = sm; r.sj = sj;
     const size_t total = (size_t)pl.m_pad * pl.j_pad;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, r);
+    r.dw_blocks = (int)((total + 255) / 256);
+    const int db_blocks = db != nullptr ? ceil_div(mtot, 64) : 0;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(r.dw_blocks + db_blocks)), dim3(256), 0, st, r);
     VCG_LAUNCH_CHECK();
-    if (db != nullptr) {
-        hipLaunchKernelGGL(wgrad_db_reduce_kernel, dim3(ceil_div(mtot, 64)), dim3(256), 0, st, (const float*)p.dbpart, db,
-                           pl.slabs, pl.m_pad, mtot);
-        VCG_LAUNCH_CHECK();
-    }
     return VCG_OK;
 }
