@@ -68,6 +68,11 @@ const char* vcg_error_string(int code);
 
 /* ---- Conv2D: keras.layers.Conv2D at upscaling/upscaler/model.py:19,22,275,283,290 (generator),
  *      :839-871 / :904-936 (discriminators), :65 (downsampling_block) -------------------------- */
+/* Size limit of the MFMA convolution kernels behind vcg_conv2d_fwd, vcg_conv2d_fwd_stats, vcg_conv2d_dgrad (stride 1, and stride 2 of a
+ * Conv2DTranspose: vcg_conv_transpose2d_dgrad) whenever the launch produces more than 32 / kw channels: they address one image's block of 64
+ * result channels through a buffer descriptor with 32-bit byte offsets, so 64 * rows * columns * 4 bytes of the RESULT (y, or dx for a data
+ * gradient; whatever its channel count) must stay below 0xFFFFFFE0, i.e. 16.7 M pixels per image, and so must 8 planes of the tensor they read.
+ * Larger shapes return VCG_E_UNSUPPORTED before anything is launched.  (1080 x 1920 frames are 2.07 M pixels.) */
 int vcg_conv2d_fwd(const vcg_conv_desc* d, const float* x, const float* w_hwio, float* y,
                    const vcg_epilogue* ep, vcg_stream_t stream);
 /* vcg_conv2d_fwd (+ bias, no activation) whose epilogue also leaves the statistics of the BatchNormalization / instance norm that follows

@@ -52,64 +52,87 @@ struct ConvCfg {
 };
 
 // ---- shared epilogue: y = act(acc + bias) + residual for a 64-channel x (8 rows x 32*XT cols) tile ----------
+// The (image, 64-channel block) of y -- and of the residual -- is one buffer descriptor and every address a 32-bit byte
+// offset into it.  A lane keeps one offset per (row, x-tile) of its 2 x XT accumulator tiles: rows and columns past the
+// ragged edge get VCG_OOB there, once per tile.  An element adds its channel's scalar multiple of the plane with a
+// SATURATING add, so VCG_OOB stays out of range whatever is added (a wrapping add would bring it back into the block);
+// channels past cout land behind num_records on their own.  The hardware drops what is out of range: one straight-line
+// body, no exec-mask region.  The range check sees the VGPR offset only, which is why nothing sits in soffset.
+// conv_block_fits() (host) keeps 64 planes below 4 GiB.
 template <int XT>
 __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)[2][2][XT], int n, int co0, int oy0, int ox0,
                                               int wv, int lane) {
-    constexpr int ROWS_ = 8;
     const int half = lane >> 5, l31 = lane & 31;
-    // epilogue: y = act(acc + bias) + residual.  Interior tiles take a guard-free path.
-    const int ox = ox0 + l31;
-    const bool full = (co0 + 64 <= p.cout) && (oy0 + ROWS_ <= p.oh) && (ox0 + 32 * XT <= p.ow);
-    // 32-bit element offsets inside this image's [cout][oh][ow] block: one scalar base + a vector offset
-    const int plane = p.oh * p.ow;
-    const size_t img = (size_t)n * p.cout * plane;
-    float* yb = p.y + img;
-    const float* rb = p.residual ? p.residual + img : nullptr;
-    const int ob = (co0 + 4 * half) * plane + (oy0 + wv * 2) * p.ow + ox;
+    const unsigned plane = (unsigned)(p.oh * p.ow), plane4 = 4u * plane, ow4 = 4u * (unsigned)p.ow;
+    const int nch = p.cout - co0 < 64 ? p.cout - co0 : 64;
+    const size_t blk = ((size_t)n * p.cout + co0) * plane;
+    const size_t blk_bytes = (size_t)nch * plane * sizeof(float);
+    const vcg_rsrc ry = make_rsrc(p.y + blk, blk_bytes);
+    const vcg_rsrc rr = make_rsrc(p.residual ? p.residual + blk : nullptr, p.residual ? blk_bytes : 0);
     // none / LeakyReLU / PReLU share one straight-line form  v >= 0 ? v : v*slope  (slope 1 = identity);
-    // tanh is only offered by the small-M kernel (the API rejects it here).
-    const float* bp = p.bias ? p.bias : vcg_zero_word;
-    const int bmask = p.bias ? ~0 : 0;
+    // tanh is only offered by the small-M kernel (the API rejects it here).  A missing bias / slope vector is an empty
+    // descriptor: every load from it returns 0, like the loads of the channels past cout
     const bool is_prelu = p.act == VCG_ACT_PRELU;
-    const float* ap = is_prelu ? p.prelu : vcg_zero_word;
-    const int amask = is_prelu ? ~0 : 0;
+    const vcg_rsrc rbias = make_rsrc(p.bias, p.bias ? (size_t)p.cout * sizeof(float) : 0);
+    const vcg_rsrc rslope = make_rsrc(is_prelu ? p.prelu : nullptr, is_prelu ? (size_t)p.cout * sizeof(float) : 0);
     const float slope_u = (p.act == VCG_ACT_LRELU) ? p.alpha : 1.f;
-    auto emit = [&](auto guard_tag, auto res_tag) {
-        constexpr bool GUARD = decltype(guard_tag)::value, RES = decltype(res_tag)::value;
+    const unsigned chan4 = 4u * (unsigned)(co0 + 4 * half);
+
+    const int oy = oy0 + wv * 2, ox = ox0 + l31;
+    const unsigned base = (unsigned)(4 * half) * plane4 + (unsigned)oy * ow4 + 4u * (unsigned)ox;
+    unsigned vo[2][XT];
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
+    for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = mt * 32 + mfma_row(r, lane);
-                const int co = co0 + row;
-                const bool co_ok = !GUARD || co < p.cout;
-                const int cs = co_ok ? co : co0;
-                const float bv = bp[cs & bmask];
-                const float pa = ap[cs & amask];
-                const float al = is_prelu ? pa : slope_u;
+        for (int xt = 0; xt < XT; ++xt)
+            vo[rt][xt] = (oy + rt < p.oh && ox + xt * 32 < p.ow) ? base + (unsigned)rt * ow4 + 128u * xt : VCG_OOB;
+
+    // 16 elements = RG accumulator rows (channels) make a group; the residual of group g + 1 is requested before group g
+    // is stored, so a group never waits for the stores in front of its own loads
+    constexpr int RG = 8 / XT, NG = 32 / RG;
+    auto emit = [&](auto res_tag) {
+        constexpr bool RES = decltype(res_tag)::value;
+        float rs[2][RG][2][XT];
+        auto row_of = [](int g, int j) { const int q = g * RG + j, r = q & 15; return (q >> 4) * 32 + (r & 3) + 8 * (r >> 2); };
+        auto load_res = [&](int g) {
+#pragma unroll
+            for (int j = 0; j < RG; ++j) {
+                const unsigned srow = (unsigned)row_of(g, j) * plane4;
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                    for (int xt = 0; xt < XT; ++xt) rs[g & 1][j][rt][xt] = buf_load(rr, __builtin_elementwise_add_sat(vo[rt][xt], srow));
+            }
+        };
+        if (RES) load_res(0);
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            float bv[RG], al[RG];
+#pragma unroll
+            for (int j = 0; j < RG; ++j) {
+                bv[j] = buf_load(rbias, chan4 + 4u * (unsigned)row_of(g, j));
+                const float pa = buf_load(rslope, chan4 + 4u * (unsigned)row_of(g, j));
+                al[j] = is_prelu ? pa : slope_u;
+            }
+            if (RES && g + 1 < NG) load_res(g + 1);
+#pragma unroll
+            for (int j = 0; j < RG; ++j) {
+                const int q = g * RG + j;
+                const unsigned srow = (unsigned)row_of(g, j) * plane4;
 #pragma unroll
                 for (int rt = 0; rt < 2; ++rt) {
 #pragma unroll
                     for (int xt = 0; xt < XT; ++xt) {
-                        const int o = ob + (row - 4 * half) * plane + rt * p.ow + xt * 32;
-                        if (!GUARD || (co_ok && oy0 + wv * 2 + rt < p.oh && ox + xt * 32 < p.ow)) {
-                            float v = acc[mt][rt][xt][r] + bv;
-                            v = v >= 0.f ? v : v * al;
-                            if (RES) v += rb[o];
-                            yb[o] = v;
-                        }
+                        float v = acc[q >> 4][rt][xt][q & 15] + bv[j];
+                        v = v >= 0.f ? v : v * al[j];
+                        if (RES) v += rs[g & 1][j][rt][xt];
+                        buf_store(ry, __builtin_elementwise_add_sat(vo[rt][xt], srow), v);
                     }
                 }
             }
         }
     };
-    using T_ = std::true_type;
-    using F_ = std::false_type;
-    if (full) {
-        if (rb) emit(F_{}, T_{}); else emit(F_{}, F_{});
-    } else {
-        if (rb) emit(T_{}, T_{}); else emit(T_{}, F_{});
-    }
+    if (p.residual) emit(std::true_type{}); else emit(std::false_type{});
 }
 
 // STATS epilogue: for the BatchNormalization / instance norm behind the convolution (model.py:19-25, 840) the workgroup also leaves, per output
@@ -173,22 +196,6 @@ __global__ __launch_bounds__(256, (KH >= 9 ? 1 : 2)) void conv_fwd_kernel(const 
 
     float rin[C::IN_PT], rw[C::W_PT];
 
-    // per-thread input BYTE offsets inside a chunk's [CK][h][w] block, computed once (VCG_OOB = zero padding); a chunk
-    // only moves the descriptor's base (scalar), whose record count also cuts off the channels past cin: the
-    // staging loop is one buffer_load per element, no per-element VALU and nothing that depends on the loaded data
-    unsigned in_off[C::IN_PT];
-#pragma unroll
-    for (int i = 0; i < C::IN_PT; ++i) {
-        const int e = tid + i * 256;
-        unsigned off = VCG_OOB;
-        if (e < C::IN_ELEMS) {
-            const int ci = e / C::PLANE, rem = e % C::PLANE;
-            const int r = rem / C::IW, c = rem % C::IW;
-            const int gy = gy0 + r, gx = gx0 + c;
-            if (gy >= 0 && gy < p.h && gx >= 0 && gx < p.w_) off = 4u * (unsigned)((ci * p.h + gy) * p.w_ + gx);
-        }
-        in_off[i] = off;
-    }
     const int hw = p.h * p.w_;
     // weights: row q = (ci, tap) of the chunk is wave-uniform, the lane is the output channel.  Rows of channels past
     // cin alias the next tap's rows (finite values that meet zero inputs) or fall off the tensor's end (range check -> 0);
@@ -197,10 +204,8 @@ __global__ __launch_bounds__(256, (KH >= 9 ? 1 : 2)) void conv_fwd_kernel(const 
     const unsigned wcol = 4u * (unsigned)(co0 + lane < p.cout ? co0 + lane : p.cout - 1);
     const size_t wbytes = (size_t)C::T * p.cin * p.cout * sizeof(float);
 
-    auto load_chunk = [&](int ci0) {
-        const vcg_rsrc rx = make_rsrc(xn + (size_t)ci0 * hw, (size_t)(p.cin - ci0) * hw * sizeof(float));
-#pragma unroll
-        for (int i = 0; i < C::IN_PT; ++i) rin[i] = buf_load(rx, in_off[i]);
+    auto in_rsrc = [&](int ci0) { return make_rsrc(xn + (size_t)ci0 * hw, (size_t)(p.cin - ci0) * hw * sizeof(float)); };
+    auto load_w = [&](int ci0) {
         const vcg_rsrc rwt = make_rsrc(p.w + (size_t)ci0 * p.cout, wbytes - (size_t)ci0 * p.cout * sizeof(float));
 #pragma unroll
         for (int i = 0; i < C::W_PT; ++i) {
@@ -209,6 +214,49 @@ __global__ __launch_bounds__(256, (KH >= 9 ? 1 : 2)) void conv_fwd_kernel(const 
             const int tap = p.flip ? (C::T - 1 - t) : t;
             rw[i] = buf_load(rwt, 4u * (unsigned)((tap * p.cin + ci) * p.cout) + wcol);
         }
+    };
+    // the first chunk's weights need nothing of what follows: they are in flight while the input offsets are worked out
+    load_w(0);
+    __builtin_amdgcn_sched_barrier(0);                 // (the scheduler would otherwise sink them below the decode)
+
+    // per-thread input BYTE offsets inside a chunk's [CK][h][w] block, computed once (VCG_OOB = zero padding); a chunk
+    // only moves the descriptor's base (scalar), whose record count also cuts off the channels past cin: the
+    // staging loop is one buffer_load per element, no per-element VALU and nothing that depends on the loaded data.
+    // Element e = tid + 256 i is (channel, row, column) of the halo tile: decoded once for i = 0 and carried from e to
+    // e + 256 with compare-and-subtract (256 = Q1 planes + QR rows + RC columns), the byte offset along with it (modulo
+    // 2^32 while outside the map, exact inside).  Validity is a select on the offset.  Each element's load of the first
+    // chunk leaves as soon as its offset is known.
+    unsigned in_off[C::IN_PT];
+    {
+        constexpr int Q1 = 256 / C::PLANE, R1 = 256 % C::PLANE, QR = R1 / C::IW, RC = R1 % C::IW;
+        const vcg_rsrc rx = in_rsrc(0);
+        const unsigned w4 = 4u * (unsigned)p.w_, hw4 = 4u * (unsigned)hw;
+        const unsigned step = (unsigned)Q1 * hw4 + (unsigned)QR * w4 + 4u * RC;
+        const unsigned col_wrap = w4 - 4u * C::IW, row_wrap = hw4 - (unsigned)C::IH * w4;
+        int ci = tid / C::PLANE, r = (tid % C::PLANE) / C::IW, c = (tid % C::PLANE) % C::IW;
+        unsigned off = (unsigned)ci * hw4 + (unsigned)(gy0 + r) * w4 + 4u * (unsigned)(gx0 + c);
+#pragma unroll
+        for (int i = 0; i < C::IN_PT; ++i) {
+            const bool in_tile = (i + 1) * 256 <= C::IN_ELEMS || ci < CK;
+            const bool ok = in_tile && (unsigned)(gy0 + r) < (unsigned)p.h && (unsigned)(gx0 + c) < (unsigned)p.w_;
+            in_off[i] = ok ? off : VCG_OOB;
+            rin[i] = buf_load(rx, in_off[i]);
+            __builtin_amdgcn_sched_barrier(0);         // keep the load here, not gathered behind the last offset
+            c += RC;
+            const bool cw = c >= C::IW;
+            c -= cw ? C::IW : 0;
+            r += QR + (cw ? 1 : 0);
+            const bool rwr = r >= C::IH;
+            r -= rwr ? C::IH : 0;
+            ci += Q1 + (rwr ? 1 : 0);
+            off += step + (cw ? col_wrap : 0u) + (rwr ? row_wrap : 0u);
+        }
+    }
+    auto load_chunk = [&](int ci0) {
+        const vcg_rsrc rx = in_rsrc(ci0);
+#pragma unroll
+        for (int i = 0; i < C::IN_PT; ++i) rin[i] = buf_load(rx, in_off[i]);
+        load_w(ci0);
     };
     auto store_chunk = [&]() {
 #pragma unroll
@@ -237,7 +285,6 @@ __global__ __launch_bounds__(256, (KH >= 9 ? 1 : 2)) void conv_fwd_kernel(const 
     const float* abase = s_w + half * C::T * 64 + l31;
 
     const int nchunks = (p.cin + CK - 1) / CK;
-    load_chunk(0);
     for (int c = 0; c < nchunks; ++c) {
         __syncthreads();
         store_chunk();
@@ -595,9 +642,19 @@ int launch_with_lds(Kern kern, int grid, size_t lds, const ConvParams& p, hipStr
     return VCG_OK;
 }
 
+// conv_epilogue addresses the (image, 64-channel block) of y it writes through one buffer descriptor with 32-bit byte
+// offsets: all 64 rows of the tile form one, the rows past cout included (they must land behind num_records, not wrap
+// around), so 64 planes must stay below the descriptor's 0xFFFFFFE0 ceiling; the staging loads a chunk of ck input
+// planes likewise
+bool conv_block_fits(int oh, int ow, int ck, int h, int w) {
+    const unsigned long long lim = 0xFFFFFFE0ull;
+    return 64ull * oh * ow * sizeof(float) < lim && (unsigned long long)ck * h * w * sizeof(float) < lim;
+}
+
 template <int KH, int KW, int S, int CK, int XT>
 int launch_conv(ConvParams p, hipStream_t st) {
     using C = ConvCfg<KH, KW, S, CK, XT>;
+    if (!conv_block_fits(p.oh, p.ow, CK, p.h, p.w_)) return VCG_E_UNSUPPORTED;
     p.tiles_x = ceil_div(p.ow, 32 * XT);
     p.tiles_y = ceil_div(p.oh, C::ROWS);
     p.co_blocks = ceil_div(p.cout, 64);
@@ -616,6 +673,7 @@ int launch_conv(ConvParams p, hipStream_t st) {
 template <int KH, int KW, int S>
 int launch_c3(ConvParams p, hipStream_t st) {
     using C = C3Cfg<KH, KW, S>;
+    if (!conv_block_fits(p.oh, p.ow, 3, p.h, p.w_)) return VCG_E_UNSUPPORTED;
     p.tiles_x = ceil_div(p.ow, 32);
     p.tiles_y = ceil_div(p.oh, C::ROWS);
     p.co_blocks = ceil_div(p.cout, 64);

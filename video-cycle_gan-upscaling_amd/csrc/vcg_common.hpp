@@ -99,6 +99,12 @@ __device__ __forceinline__ float buf_load(vcg_rsrc r, unsigned byte_off) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)byte_off, 0, 0));
 }
 
+// store through a descriptor: an offset at or past num_records (VCG_OOB, a channel past the end) is dropped by the
+// hardware.  The range check sees the VGPR offset only: keep what decides validity out of soffset.
+__device__ __forceinline__ void buf_store(vcg_rsrc r, unsigned byte_off, float v) {
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)byte_off, 0, 0);
+}
+
 // wave64 sum via DPP-free shuffles
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
