@@ -104,7 +104,7 @@ def test_conv_in_gate_bf16(rt, n, h, w, cin, k, cout):
 def test_conv_in_gate_bf16_sigmoid_alone(rt):
     """m == 1 pins the sigmoid.  Bound per element: 2^-8 s + s (1 - s) da + 3e-7:
       * one rounding of s to bf16 -- 8 significant bits, half an ulp is at most 2^-8 s;
-      * 3e-7: the absolute error of the v_exp_f32 / v_rcp_f32 sigmoid (bf16_conv.hip, fast_sigmoid);
+      * 3e-7: the absolute error of the v_exp_f32 / v_rcp_f32 sigmoid (bf16_conv3x3_3ch.hip, fast_sigmoid);
       * da: the fp32 accumulation of the pre-activation a, moved through the sigmoid's slope s (1 - s).  The kernel adds 2 sources x 5 rows x
         8 columns x 4 channels = 320 products (zero-weight slots included) and the bias, each addition rounding a partial sum that
         sum |u| |w| + |bias| =: A bounds, so da <= 321 * 2^-24 * A, with A computed here from the operands."""

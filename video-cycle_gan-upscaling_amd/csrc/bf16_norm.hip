@@ -1,6 +1,6 @@
 // bf16-storage normalisation kernels (activations bf16 NHWC; statistics, affine and activation arithmetic fp32):
 // BatchNormalization / instance norm + PReLU / LeakyReLU + Add of residual_block (upscaling/upscaler/model.py:20-25)
-// on the layout of bf16_conv.hip.  HBM-bound: a thread owns 8 consecutive channels (16 bytes) of a pixel; the
+// on the layout of the bf16 convolutions (bf16_tiles.hpp).  HBM-bound: a thread owns 8 consecutive channels (16 bytes) of a pixel; the
 // per-channel reductions run over pixels, so a wavefront's 8 lanes of one pixel never have to exchange anything and
 // the cross-pixel sums go through LDS once per block.  vcg_norm_finalize (fp32, norm.hip) turns the statistics
 // into scale / shift and maintains the moving averages exactly as on the fp32 path.

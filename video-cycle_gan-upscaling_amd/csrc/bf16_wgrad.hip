@@ -16,6 +16,7 @@
 //     pixels fetched from a zero page);
 //   * per-wave partial blocks go to the workspace and are summed in a fixed order (deterministic) into Keras' layout.
 #include "vcg_common.hpp"
+#include "vcg_stamps.hpp"
 
 namespace {
 
@@ -39,22 +40,12 @@ struct WgParams {
     int n, h, w_, tiles_x, tiles_y, total;
 };
 
-// Diagnostic build only (-DVCG_WG_STAMPS, scripts/micro/wg_stamps.sh): per wave, s_memtime sums of [wait for the stage's DMA, barrier, DMA issue,
+// Diagnostic build only (-DVCG_STAMPS, scripts/micro/stamps.py): per wave, s_memtime sums of [wait for the stage's DMA, barrier, DMA issue,
 // k-steps, tiles, kernel clocks]
-#ifdef VCG_WG_STAMPS
-__device__ unsigned long long vcg_wg_stamp_sums[256 * G_NWT * 6];
-#define WG_STAMP(t)                                                                   \
-    do {                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                            \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");     \
-        __builtin_amdgcn_sched_barrier(0);                                            \
-    } while (0)
-#else
-#define WG_STAMP(t) do { } while (0)
-#endif
+VCG_STAMP_SUMS(wg, 256 * G_NWT * 6);
 
 __global__ __launch_bounds__(G_NWT * 64, 1) void wgrad3x3_c64_bf16_kernel(WgParams p) {
-#ifdef VCG_WG_STAMPS
+#ifdef VCG_STAMPS
     unsigned long long ws0 = 0, ws1 = 0, ws2 = 0, ws3 = 0, wcnt = 0, wt0, wt1, wt2, wt3, wt4;
     const unsigned long long wk0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -94,7 +85,7 @@ __global__ __launch_bounds__(G_NWT * 64, 1) void wgrad3x3_c64_bf16_kernel(WgPara
                 for (int e = 0; e < 16; ++e) acc[a][b][c][e] = 0.f;
 
     const long img_bytes = (long)p.h * p.w_ * 128;
-    // Staging belongs to two LOADER waves (wv >= G_NW), 38 1-KiB pieces each per stage.  In-kernel stamps (scripts/micro/wg_stamps.*,
+    // Staging belongs to two LOADER waves (wv >= G_NW), 38 1-KiB pieces each per stage.  In-kernel stamps (scripts/micro/stamps.py run wg,
     // profiles/r03_wg_stamps.txt) of the form in which the six compute waves issued 13 pieces each: 2.6-3.7 k of a tile's 11.2 k ticks in
     // the issue block behind the barrier (every `buffer_load ... lds` waits for room in the CU's memory pipe; no wave multiplies meanwhile)
     // and next to nothing waiting for the data afterwards; with the pieces spread over the k-steps the same ticks moved into the k-steps
@@ -151,19 +142,19 @@ __global__ __launch_bounds__(G_NWT * 64, 1) void wgrad3x3_c64_bf16_kernel(WgPara
         int tile = blockIdx.x, buf = 0;
         if (tile < p.total) issue(tile, 0);
         for (; tile < p.total; tile += gridDim.x, buf ^= 1) {
-            WG_STAMP(wt0);
+            VCG_STAMP(wt0);
             __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): this wave's half of the stage has landed
-            WG_STAMP(wt1);
+            VCG_STAMP(wt1);
             lds_barrier();
-            WG_STAMP(wt2);
+            VCG_STAMP(wt2);
             const int next = tile + gridDim.x;
             if (next < p.total) issue(next, buf ^ 1);
-            WG_STAMP(wt3);
-#ifdef VCG_WG_STAMPS
+            VCG_STAMP(wt3);
+#ifdef VCG_STAMPS
             ws0 += wt1 - wt0, ws1 += wt2 - wt1, ws2 += wt3 - wt2, ++wcnt;
 #endif
         }
-#ifdef VCG_WG_STAMPS
+#ifdef VCG_STAMPS
         if (lane == 0 && blockIdx.x < 256) {
             unsigned long long* o = vcg_wg_stamp_sums + (blockIdx.x * G_NWT + wv) * 6;
             o[0] = ws0, o[1] = ws1, o[2] = ws2, o[3] = 0, o[4] = wcnt, o[5] = __builtin_amdgcn_s_memtime() - wk0;
@@ -176,11 +167,11 @@ __global__ __launch_bounds__(G_NWT * 64, 1) void wgrad3x3_c64_bf16_kernel(WgPara
 
     int tile = blockIdx.x, buf = 0;
     for (; tile < p.total; tile += gridDim.x, buf ^= 1) {
-        WG_STAMP(wt0);
-        WG_STAMP(wt1);
+        VCG_STAMP(wt0);
+        VCG_STAMP(wt1);
         lds_barrier();                               // the loaders' stage has landed; the other buffer is free again
-        WG_STAMP(wt2);
-        WG_STAMP(wt3);
+        VCG_STAMP(wt2);
+        VCG_STAMP(wt3);
         const unsigned lb = lds0 + buf * G_BUF;
 
         // 8 k-steps of 16 pixels: rows ph*4 .. ph*4+3, column halves 0/1
@@ -225,12 +216,12 @@ __global__ __launch_bounds__(G_NWT * 64, 1) void wgrad3x3_c64_bf16_kernel(WgPara
                     }
                 }
         });
-        WG_STAMP(wt4);
-#ifdef VCG_WG_STAMPS
+        VCG_STAMP(wt4);
+#ifdef VCG_STAMPS
         ws0 += wt1 - wt0, ws1 += wt2 - wt1, ws2 += wt3 - wt2, ws3 += wt4 - wt3, ++wcnt;
 #endif
     }
-#ifdef VCG_WG_STAMPS
+#ifdef VCG_STAMPS
     if (lane == 0 && blockIdx.x < 256) {
         unsigned long long* o = vcg_wg_stamp_sums + (blockIdx.x * G_NWT + wv) * 6;
         o[0] = ws0, o[1] = ws1, o[2] = ws2, o[3] = ws3, o[4] = wcnt, o[5] = __builtin_amdgcn_s_memtime() - wk0;
@@ -350,12 +341,5 @@ int vcg_conv2d_bf16_wgrad(const vcg_conv_desc* d, const void* x, const void* dy,
     VCG_LAUNCH_CHECK();
     return VCG_OK;
 }
-
-#ifdef VCG_WG_STAMPS
-int vcg_debug_wg_stamps(unsigned long long* host_out) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(vcg_wg_stamp_sums), sizeof(unsigned long long) * 256 * G_NWT * 6);
-}
-#endif
 
 }  // extern "C"

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(R_NW * 64, 1) void conv9x9_rowchain_f32_kernel(RowC
         // (channel slot/18, columns 4*(slot%18)..+3) is recomputed per row from an opaque lane index: nine hoisted 64-bit lane pointers
         // were SPILLED at this kernel's 256-register budget, and hipcc waits vmcnt(0) in front of every scratch reload -- i.e. for every
         // piece issued before it: the pieces went out one HBM round trip after the other (the same defect, measured, in
-        // bf16_conv.hip: conv9x9_c256to3_bf16_kernel, profiles/r03_f9_stamps.txt).
+        // bf16_conv9x9_to3.hip: conv9x9_c256to3_bf16_kernel, profiles/r03_f9_stamps.txt).
         const vcg_rsrc rs = make_rsrc(xin, (size_t)R_CI * plane * 4);
         auto dma = [&](int yi, int buf) {
             const bool rowok = (unsigned)yi < (unsigned)p.h;

@@ -173,6 +173,15 @@ SIGNATURES = {
 _lib = None
 
 
+def bind(lib):
+    """Give every declared symbol of a loaded library its restype / argtypes (also used on diagnostic builds of the library)."""
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
 def load():
     """dlopen libvcg_hip.so and bind every declared symbol.  Raises RuntimeError on failure."""
     global _lib
@@ -186,11 +195,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise RuntimeError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
+    _lib = bind(lib)
     return lib
 
 
