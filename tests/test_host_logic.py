@@ -298,6 +298,50 @@ def test_conv2d_bf16_constructor_only_accepts_trainable_shapes():
             E.Conv2DBf16("bad", bad[0], bad[1], bad[2], bad[3], "same")
 
 
+def test_packed_operand_builds_lazily_into_buffers_that_never_move():
+    """E.PackedOperand with a fake build (no device): one build per stale period, none from refresh() itself, the same buffer objects
+    before and after a refresh (a captured train step re-packs into their addresses), and two operands of one layer rebuilt each on
+    its own demand (FirstConvBf16: the bf16 fragments every step, _wt only in the fp32 data-gradient fallback)"""
+    from upscaler import _engine as E
+    layer = E.Layer("l")
+    log = []
+
+    def fake_build(tag):
+        def build(bufs):
+            log.append((tag, bufs))
+            return [tag] if bufs is None else bufs          # allocate on first use only
+        return build
+
+    a, b = E.PackedOperand(fake_build("a"), layer), E.PackedOperand(fake_build("b"), layer)
+    assert layer.caches == [a, b] and log == []             # nothing is built before it is asked for
+    buf_a = a.get()
+    assert a.get() is buf_a and a.get() is buf_a
+    assert log == [("a", None)]                             # once, and b not at all
+    layer.refresh()
+    layer.refresh()
+    assert log == [("a", None)]                             # refresh() marks stale; it builds nothing
+    assert a.get() is buf_a and a.get() is buf_a            # the same object after the refresh
+    assert len(log) == 2 and log[1][0] == "a" and log[1][1] is buf_a        # rebuilt once, into the buffers it already had
+    buf_b = b.get()                                         # b: first asked for now, after two refreshes -- one build
+    assert [t for t, _ in log] == ["a", "a", "b"] and log[2][1] is None
+    layer.refresh()
+    assert b.get() is buf_b and [t for t, _ in log] == ["a", "a", "b", "b"]  # b rebuilt; a stays stale until it is asked for
+    assert a.get() is buf_a and [t for t, _ in log] == ["a", "a", "b", "b", "a"]
+    # a build that hands back other buffers on a rebuild does not move the operand
+    moving = E.PackedOperand(lambda bufs: [object()], layer)
+    first = moving.get()
+    layer.refresh()
+    assert moving.get() is first
+    # a layer class's operands are registered by its constructor: Layer.refresh() reaches them without an override
+    conv = E.FirstConvBf16("c", 3, 64, 3)
+    assert len(conv.caches) == 2 and all(c.stale for c in conv.caches)
+    for c in conv.caches:
+        c.stale = False
+    conv.refresh()
+    assert all(c.stale for c in conv.caches)
+    assert "refresh" not in E.FirstConvBf16.__dict__ and "refresh" not in E.Conv2D.__dict__
+
+
 def test_fused_step_is_opt_in_and_oracle_restates_it():
     """the faithful three-call step is the default everywhere; `fused_step` is an extension keyword behind the reference's arguments"""
     import inspect

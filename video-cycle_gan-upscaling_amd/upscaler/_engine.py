@@ -180,6 +180,7 @@ class Layer:
         self.name = name
         self.rt = None
         self.ps = None
+        self.caches = []        # the layer's PackedOperands
 
     def bind(self, rt, ps):
         self.rt, self.ps = rt, ps
@@ -189,6 +190,48 @@ class Layer:
 
     def refresh(self):
         """called after the parameters changed (optimizer step / set_weights)"""
+        for c in self.caches:
+            c.stale = True
+
+
+class PackedOperand:
+    """Device copy of a layer's kernel in the layout a kernel reads.  ``build(bufs)`` fills the buffers from the parameters (bufs None on
+    first use: it allocates them) and returns them; it runs when the copy is asked for while stale, never on refresh() itself.
+
+    The buffers keep their addresses for the life of the layer: get() stores what build returns only once and hands build the same
+    buffers back ever after.  A captured train step has the pack launches and the kernels reading these addresses baked into its nodes;
+    a buffer replaced after an optimizer step would leave the graph re-packing into, and reading from, freed memory."""
+
+    def __init__(self, build, *layers):
+        self.build, self.bufs, self.stale = build, None, True
+        for l in layers:
+            l.caches.append(self)
+
+    def get(self):
+        if self.stale:
+            bufs = self.build(self.bufs)
+            self.bufs = bufs if self.bufs is None else self.bufs
+            self.stale = False
+        return self.bufs
+
+
+def act_bwd_bias(layer, y, dy, d, param_grads, which):
+    """backward of a convolution's fused activation: dz = act'(y) * dy, the bias gradient (per-channel sum of dz) out of the same pass"""
+    rt = layer.rt
+    hw = d.oh * d.ow
+    dz = rt.empty(*dy.shape)
+    db = layer.ps.grad(layer.name + "/bias", which).data_ptr() if param_grads else None
+    ws, wsn = rt.workspace(rt.lib.vcg_act_bwd_workspace_bytes(d.n, layer.cout, hw))
+    L.check(rt.lib.vcg_act_bwd(y.data_ptr(), dy.data_ptr(), d.n, layer.cout, hw, layer.act, float(layer.alpha),
+                               None, dz.data_ptr(), None, db, ws, wsn, rt.stream), "vcg_act_bwd[%s]" % layer.name)
+    return dz
+
+
+def kernel_transpose(rt, w, taps, a, b, out=None):
+    """fp32 per-tap transpose of a kernel [taps][a][b] -> [taps][b][a] (the fp32 data-gradient / transposed-convolution operand)"""
+    out = rt.empty(taps, b, a) if out is None else out
+    L.check(rt.lib.vcg_kernel_transpose(w.data_ptr(), out.data_ptr(), taps, a, b, rt.stream), "vcg_kernel_transpose")
+    return out
 
 
 class Conv2D(Layer):
@@ -199,8 +242,8 @@ class Conv2D(Layer):
         self.kh, self.kw = (int(k[0]), int(k[1])) if isinstance(k, (tuple, list)) else (int(k), int(k))
         self.cin, self.cout, self.k, self.stride, self.padding = cin, cout, self.kh, stride, padding     # k: the square layers' size
         self.act, self.alpha = act, alpha
-        self.wt = None
-        self._wt_valid = False
+        # per-tap transposed kernel (kh,kw,out,in): the fp32 data gradient's second operand
+        self._wt = PackedOperand(lambda out: kernel_transpose(self.rt, self.ps[self.name + "/kernel"], self.kh * self.kw, self.cin, self.cout, out), self)
 
     def declare(self, ps):
         ps.declare(self.name + "/kernel", (self.kh, self.kw, self.cin, self.cout))
@@ -226,20 +269,6 @@ class Conv2D(Layer):
     def desc(self, n, h, w):
         oh, ow, pt, pl = self.out_hw(h, w)
         return L.ConvDesc(n, self.cin, h, w, self.cout, oh, ow, self.kh, self.kw, self.stride, pt, pl)
-
-    def refresh(self):
-        self._wt_valid = False
-
-    def _wt(self):
-        """per-tap transposed kernel (kh,kw,out,in), rebuilt lazily after each parameter change"""
-        rt = self.rt
-        if self.wt is None:
-            self.wt = rt.empty(self.kh * self.kw, self.cout, self.cin)
-        if not self._wt_valid:
-            L.check(rt.lib.vcg_kernel_transpose(self.ps[self.name + "/kernel"].data_ptr(), self.wt.data_ptr(),
-                                                self.kh * self.kw, self.cin, self.cout, rt.stream), "vcg_kernel_transpose")
-            self._wt_valid = True
-        return self.wt
 
     def forward(self, x, residual=None, tag=None):
         rt = self.rt
@@ -276,25 +305,11 @@ class Conv2D(Layer):
         rt = self.rt
         x, y, d = ctx
         n = d.n
-        db_done = False
-        if self.act != L.ACT_NONE:
-            # activation backward; the bias gradient (per-channel sum of dz) comes out of the same pass
-            dz = rt.empty(*dy.shape)
-            db = self.ps.grad(self.name + "/bias", which).data_ptr() if param_grads else None
-            ws, wsn = rt.workspace(rt.lib.vcg_act_bwd_workspace_bytes(n, self.cout, d.oh * d.ow))
-            L.check(rt.lib.vcg_act_bwd(y.data_ptr(), dy.data_ptr(), n, self.cout, d.oh * d.ow, self.act, float(self.alpha),
-                                       None, dz.data_ptr(), None, db, ws, wsn, rt.stream), "vcg_act_bwd[%s]" % self.name)
-            dy = dz
-            db_done = True
+        db_done = self.act != L.ACT_NONE
+        if db_done:
+            dy = act_bwd_bias(self, y, dy, d, param_grads, which)
         if param_grads:
-            need = rt.lib.vcg_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
-            ws, wsn = rt.workspace(need)
-            with Timed(rt, tag and tag + "_wgrad"):
-                L.check(rt.lib.vcg_conv2d_wgrad(ctypes.byref(d), x.data_ptr(), dy.data_ptr(),
-                                                self.ps.grad(self.name + "/kernel", which).data_ptr(),
-                                                None if db_done else self.ps.grad(self.name + "/bias", which).data_ptr(),
-                                                ws, wsn, rt.stream),
-                        "vcg_conv2d_wgrad[%s]" % self.name)
+            self._wgrad_fp32(d, x, dy, which, not db_done, tag)
         dx = None
         if need_dx:
             dx = rt.empty(n, self.cin, d.h, d.w)
@@ -307,9 +322,18 @@ class Conv2D(Layer):
                 dd = L.ConvDesc(n, self.cin, d.h, d.w, self.cout, dyd.shape[2], dyd.shape[3], self.kh, self.kw, 1, d.pad_top, d.pad_left)
             with Timed(rt, tag and tag + "_dgrad"):
                 L.check(rt.lib.vcg_conv2d_dgrad(ctypes.byref(dd), dyd.data_ptr(), self.ps[self.name + "/kernel"].data_ptr(),
-                                                self._wt().data_ptr(), dx.data_ptr(), _ptr(dx_residual), rt.stream),
+                                                self._wt.get().data_ptr(), dx.data_ptr(), _ptr(dx_residual), rt.stream),
                         "vcg_conv2d_dgrad[%s]" % self.name)
         return dx
+
+    def _wgrad_fp32(self, d, x, dy, which, with_bias, tag):
+        """fp32 weight gradient of the convolution d from fp32 NCHW x and dy (with_bias: and the bias gradient, the per-channel sum of dy)"""
+        rt = self.rt
+        ws, wsn = rt.workspace(rt.lib.vcg_conv2d_wgrad_workspace_bytes(ctypes.byref(d)))
+        with Timed(rt, tag and tag + "_wgrad"):
+            L.check(rt.lib.vcg_conv2d_wgrad(ctypes.byref(d), x.data_ptr(), dy.data_ptr(), self.ps.grad(self.name + "/kernel", which).data_ptr(),
+                                            self.ps.grad(self.name + "/bias", which).data_ptr() if with_bias else None, ws, wsn, rt.stream),
+                    "vcg_conv2d_wgrad[%s]" % self.name)
 
 
 class ConvT2D(Layer):
@@ -318,8 +342,8 @@ class ConvT2D(Layer):
     def __init__(self, name, cin, cout, k, act=L.ACT_NONE, alpha=0.0):
         super().__init__(name)
         self.cin, self.cout, self.k, self.act, self.alpha = cin, cout, k, act, alpha
-        self.wt = None
-        self._wt_valid = False
+        # per-tap transposed kernel (k,k,in,out)
+        self._wt = PackedOperand(lambda out: kernel_transpose(self.rt, self.ps[self.name + "/kernel"], k * k, cout, cin, out), self)
 
     def declare(self, ps):
         ps.declare(self.name + "/kernel", (self.k, self.k, self.cout, self.cin))
@@ -334,19 +358,6 @@ class ConvT2D(Layer):
         crop = max(self.k - 2, 0) // 2
         return L.ConvDesc(n, self.cin, h, w, self.cout, 2 * h, 2 * w, self.k, self.k, 2, crop, crop)
 
-    def refresh(self):
-        self._wt_valid = False
-
-    def _wt(self):
-        rt = self.rt
-        if self.wt is None:
-            self.wt = rt.empty(self.k * self.k, self.cin, self.cout)
-        if not self._wt_valid:
-            L.check(rt.lib.vcg_kernel_transpose(self.ps[self.name + "/kernel"].data_ptr(), self.wt.data_ptr(),
-                                                self.k * self.k, self.cout, self.cin, rt.stream), "vcg_kernel_transpose")
-            self._wt_valid = True
-        return self.wt
-
     def forward(self, x, tag=None):
         rt = self.rt
         n, _, h, w = x.shape
@@ -354,22 +365,16 @@ class ConvT2D(Layer):
         y = rt.empty(n, self.cout, d.oh, d.ow)
         ep = L.Epilogue(_ptr(self.ps[self.name + "/bias"]), self.act, float(self.alpha), None, None)
         with Timed(rt, tag):
-            L.check(rt.lib.vcg_conv_transpose2d_fwd(ctypes.byref(d), x.data_ptr(), self._wt().data_ptr(), y.data_ptr(),
+            L.check(rt.lib.vcg_conv_transpose2d_fwd(ctypes.byref(d), x.data_ptr(), self._wt.get().data_ptr(), y.data_ptr(),
                                                     ctypes.byref(ep), rt.stream), "vcg_conv_transpose2d_fwd[%s]" % self.name)
         return y, (x, y if self.act != L.ACT_NONE else None, d)
 
     def backward(self, ctx, dy, need_dx=True, param_grads=True, which=0, tag=None):
         rt = self.rt
         x, y, d = ctx
-        db_done = False
-        if self.act != L.ACT_NONE:
-            dz = rt.empty(*dy.shape)
-            db = self.ps.grad(self.name + "/bias", which).data_ptr() if param_grads else None
-            ws, wsn = rt.workspace(rt.lib.vcg_act_bwd_workspace_bytes(d.n, self.cout, d.oh * d.ow))
-            L.check(rt.lib.vcg_act_bwd(y.data_ptr(), dy.data_ptr(), d.n, self.cout, d.oh * d.ow, self.act, float(self.alpha),
-                                       None, dz.data_ptr(), None, db, ws, wsn, rt.stream), "vcg_act_bwd[%s]" % self.name)
-            dy = dz
-            db_done = True
+        db_done = self.act != L.ACT_NONE
+        if db_done:
+            dy = act_bwd_bias(self, y, dy, d, param_grads, which)
         if param_grads:
             need = rt.lib.vcg_conv_transpose2d_wgrad_workspace_bytes(ctypes.byref(d))
             ws, wsn = rt.workspace(need)
@@ -408,16 +413,6 @@ class ConvTDilated(ConvT2D):
         # the virtual convolution: [cout, h*s, w*s] -> [cin, hd, wd], stride 1, pads (crop, crop)
         return hd, wd, L.ConvDesc(n, self.cout, h * s, w * s, self.cin, hd, wd, k, k, 1, crop, crop)
 
-    def _wt(self):
-        rt = self.rt
-        if self.wt is None:
-            self.wt = rt.empty(self.k * self.k, self.cin, self.cout)
-        if not self._wt_valid:
-            L.check(rt.lib.vcg_kernel_transpose(self.ps[self.name + "/kernel"].data_ptr(), self.wt.data_ptr(), self.k * self.k, self.cout, self.cin,
-                                                rt.stream), "vcg_kernel_transpose")
-            self._wt_valid = True
-        return self.wt
-
     def forward(self, x, tag=None):
         rt = self.rt
         n, _, h, w = x.shape
@@ -425,7 +420,7 @@ class ConvTDilated(ConvT2D):
         xd = rt.empty(n, self.cin, hd, wd)
         L.check(rt.lib.vcg_dilate2d(x.data_ptr(), xd.data_ptr(), n * self.cin, h, w, self.stride, rt.stream), "vcg_dilate2d")
         z = rt.empty(n, self.cout, d.h, d.w)
-        L.check(rt.lib.vcg_conv2d_dgrad(ctypes.byref(d), xd.data_ptr(), self.ps[self.name + "/kernel"].data_ptr(), self._wt().data_ptr(), z.data_ptr(),
+        L.check(rt.lib.vcg_conv2d_dgrad(ctypes.byref(d), xd.data_ptr(), self.ps[self.name + "/kernel"].data_ptr(), self._wt.get().data_ptr(), z.data_ptr(),
                                         None, rt.stream), "vcg_conv2d_dgrad[%s]" % self.name)
         if self._ones is None:
             self._ones = filled_like(rt, self.ps[self.name + "/bias"], 1.0)
@@ -488,22 +483,40 @@ class NormAct(Layer):
         """does forward(x, training) compute statistics of x (so that a producer's epilogue may hand them over)"""
         return self.norm is not None and bool(training or self.norm == "instance")
 
-    def forward(self, x, training, residual=None, update_moving=True, stats=None):
-        """stats: (records, records per group, shift) from the producing convolution's epilogue (Conv2D.forward_stats) -- one
-        vcg_norm_finalize_partials_shifted launch then replaces the statistics pass over x and vcg_norm_finalize"""
-        rt, ps = self.rt, self.ps
-        lib = rt.lib
+    # what NormActBf16 replaces: the entry points over the activation tensor, its shape decoding and allocation, and _finalize_partials
+    STATS, ACT_FWD, ACT_BWD = "vcg_norm_stats", "vcg_norm_act_fwd", "vcg_norm_act_bwd"
+
+    def _dims(self, x):
+        """(n, c, h*w) of fp32 NCHW or 2-D [n, c]"""
         if x.dim() == 4:
             n, c, h, w = x.shape
-            hw = h * w
-        else:
-            n, c = x.shape
-            hw = 1
-        y = rt.empty(*x.shape)
+            return n, c, h * w
+        n, c = x.shape
+        return n, c, 1
+
+    def _like(self, x):
+        return self.rt.empty(*x.shape)
+
+    def _finalize_partials(self, stats, rows, c, count, gamma, beta, eps, mean, scale, shift, invstd, mm, mv, unbiased_n):
+        """(records, records per group, shift) of Conv2D.forward_stats -> mean / scale / shift / invstd (+ moving statistics)"""
+        buf, nrec, kshift = stats
+        L.check(self.rt.lib.vcg_norm_finalize_partials_shifted(buf.data_ptr(), nrec, rows, c, count, kshift.data_ptr(), gamma, beta, eps,
+                                                               mean.data_ptr(), scale.data_ptr(), shift.data_ptr(), invstd.data_ptr(), mm, mv,
+                                                               BN_MOMENTUM, unbiased_n, self.rt.stream),
+                "vcg_norm_finalize_partials_shifted[%s]" % self.name)
+
+    def forward(self, x, training, residual=None, update_moving=True, stats=None):
+        """stats: what the producing convolution's forward_stats left behind -- one finalize-from-partials launch then replaces the
+        statistics pass over x and vcg_norm_finalize"""
+        rt, ps = self.rt, self.ps
+        lib = rt.lib
+        n, c, hw = self._dims(x)
+        y = self._like(x)
         saved = None
+        act_fwd = getattr(lib, self.ACT_FWD)
         if self.norm is None:
-            L.check(lib.vcg_norm_act_fwd(x.data_ptr(), n, c, hw, None, None, 0, self.act, float(self.alpha),
-                                         self._alpha_ptr(), _ptr(residual), y.data_ptr(), rt.stream), "vcg_norm_act_fwd")
+            L.check(act_fwd(x.data_ptr(), n, c, hw, None, None, 0, self.act, float(self.alpha),
+                            self._alpha_ptr(), _ptr(residual), y.data_ptr(), rt.stream), self.ACT_FWD)
             return y, (x, None, None, (n, c, hw))
         inst = self.norm == "instance"
         rows = n if inst else 1
@@ -511,40 +524,33 @@ class NormAct(Layer):
         scale, shift, invstd = rt.empty(rows * c), rt.empty(rows * c), rt.empty(rows * c)
         gamma = None if inst else ps[self.name + "/gamma"].data_ptr()
         beta = None if inst else ps[self.name + "/beta"].data_ptr()
-        if (training or inst) and stats is not None:
-            buf, nrec, kshift = stats
+        eps = IN_EPS if inst else BN_EPS
+        if training or inst:
             mean = rt.empty(rows * c)
-            mm = mv = None
-            if not inst and update_moving:
-                mm, mv = ps[self.name + "/moving_mean"].data_ptr(), ps[self.name + "/moving_variance"].data_ptr()
-            L.check(lib.vcg_norm_finalize_partials_shifted(buf.data_ptr(), nrec, rows, c, float(hw if inst else n * hw), kshift.data_ptr(), gamma, beta,
-                                                           IN_EPS if inst else BN_EPS, mean.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                           invstd.data_ptr(), mm, mv, BN_MOMENTUM, 0 if inst else n * hw, rt.stream),
-                    "vcg_norm_finalize_partials_shifted[%s]" % self.name)
-            saved = (mean, invstd)
-        elif training or inst:
-            mean, var = rt.empty(rows * c), rt.empty(rows * c)
-            ws, wsn = rt.workspace(lib.vcg_norm_stats_workspace_bytes(n, c, hw, mode))
-            L.check(lib.vcg_norm_stats(x.data_ptr(), n, c, hw, mode, mean.data_ptr(), var.data_ptr(), ws, wsn, rt.stream),
-                    "vcg_norm_stats[%s]" % self.name)
             mm = mv = None
             if not inst and update_moving:
                 mm, mv = ps[self.name + "/moving_mean"].data_ptr(), ps[self.name + "/moving_variance"].data_ptr()
             # Keras' TF backend: fused path (4-D) reports the Bessel-corrected variance to the moving
             # average, the 2-D path (Dense BN) the biased one
             ub = (n * hw) if (x.dim() == 4 and not inst) else 0
-            L.check(lib.vcg_norm_finalize(mean.data_ptr(), var.data_ptr(), gamma, beta, c, rows,
-                                          IN_EPS if inst else BN_EPS, scale.data_ptr(), shift.data_ptr(), invstd.data_ptr(),
-                                          mm, mv, BN_MOMENTUM, ub, rt.stream), "vcg_norm_finalize")
+            if stats is not None:
+                self._finalize_partials(stats, rows, c, float(hw if inst else n * hw), gamma, beta, eps, mean, scale, shift, invstd, mm, mv, ub)
+            else:
+                var = rt.empty(rows * c)
+                ws, wsn = rt.workspace(getattr(lib, self.STATS + "_workspace_bytes")(n, c, hw, mode))
+                L.check(getattr(lib, self.STATS)(x.data_ptr(), n, c, hw, mode, mean.data_ptr(), var.data_ptr(), ws, wsn, rt.stream),
+                        "%s[%s]" % (self.STATS, self.name))
+                L.check(lib.vcg_norm_finalize(mean.data_ptr(), var.data_ptr(), gamma, beta, c, rows, eps, scale.data_ptr(), shift.data_ptr(),
+                                              invstd.data_ptr(), mm, mv, BN_MOMENTUM, ub, rt.stream), "vcg_norm_finalize")
             saved = (mean, invstd)
         else:
             L.check(lib.vcg_norm_finalize(ps[self.name + "/moving_mean"].data_ptr(),
                                           ps[self.name + "/moving_variance"].data_ptr(), gamma, beta, c, 1, BN_EPS,
                                           scale.data_ptr(), shift.data_ptr(), invstd.data_ptr(), None, None, 0.0, 0,
                                           rt.stream), "vcg_norm_finalize")
-        L.check(lib.vcg_norm_act_fwd(x.data_ptr(), n, c, hw, scale.data_ptr(), shift.data_ptr(), 1 if inst else 0, self.act,
-                                     float(self.alpha), self._alpha_ptr(), _ptr(residual), y.data_ptr(), rt.stream),
-                "vcg_norm_act_fwd[%s]" % self.name)
+        L.check(act_fwd(x.data_ptr(), n, c, hw, scale.data_ptr(), shift.data_ptr(), 1 if inst else 0, self.act,
+                        float(self.alpha), self._alpha_ptr(), _ptr(residual), y.data_ptr(), rt.stream),
+                "%s[%s]" % (self.ACT_FWD, self.name))
         return y, (x, saved, mode, (n, c, hw))
 
     def backward(self, ctx, dy, param_grads=True, which=0):
@@ -552,7 +558,7 @@ class NormAct(Layer):
         rt, ps = self.rt, self.ps
         lib = rt.lib
         x, saved, mode, (n, c, hw) = ctx
-        dx = rt.empty(*x.shape)
+        dx = self._like(x)
         dalpha = ps.grad(self.prelu_name + "/alpha", which).data_ptr() if (self.act == L.ACT_PRELU and param_grads) else None
         if self.norm is None:
             ws, wsn = rt.workspace(lib.vcg_act_bwd_workspace_bytes(n, c, hw))
@@ -569,10 +575,10 @@ class NormAct(Layer):
         if not inst and param_grads:
             dgamma = ps.grad(self.name + "/gamma", which).data_ptr()
             dbeta = ps.grad(self.name + "/beta", which).data_ptr()
-        ws, wsn = rt.workspace(lib.vcg_norm_act_bwd_workspace_bytes(n, c, hw, mode))
-        L.check(lib.vcg_norm_act_bwd(x.data_ptr(), dy.data_ptr(), n, c, hw, mode, mean.data_ptr(), invstd.data_ptr(), gamma,
-                                     beta, self.act, float(self.alpha), self._alpha_ptr(), 1, dx.data_ptr(), dgamma, dbeta,
-                                     dalpha, ws, wsn, rt.stream), "vcg_norm_act_bwd[%s]" % self.name)
+        ws, wsn = rt.workspace(getattr(lib, self.ACT_BWD + "_workspace_bytes")(n, c, hw, mode))
+        L.check(getattr(lib, self.ACT_BWD)(x.data_ptr(), dy.data_ptr(), n, c, hw, mode, mean.data_ptr(), invstd.data_ptr(), gamma,
+                                           beta, self.act, float(self.alpha), self._alpha_ptr(), 1, dx.data_ptr(), dgamma, dbeta,
+                                           dalpha, ws, wsn, rt.stream), "%s[%s]" % (self.ACT_BWD, self.name))
         return dx
 
 
@@ -633,69 +639,93 @@ def from_bf16_nhwc(rt, x_nhwc):
     return y
 
 
-class Conv3x3Bf16(Layer):
-    """Conv2D(64, 3, 'same') on bf16 NHWC: forward and data gradient on vcg_conv2d_bf16_fwd (the latter with the kernel
-    packed tap-flipped and transposed), weight / bias gradient on vcg_conv2d_bf16_wgrad (fp32, into the master gradient)."""
+# ---- a fp32 kernel tensor w as the operand a bf16 kernel reads.  out: the buffer of an earlier call to fill again (a layer's
+# PackedOperand); None allocates one (the inference engines of _infer.py, which take fresh buffers at every refresh) ----
+def _bf16(rt, *shape):
+    return torch.empty(*shape, dtype=torch.bfloat16, device=rt.device)
 
-    def __init__(self, name, cin=64, cout=64):
-        super().__init__(name)
+
+def _bytes(rt, nbytes):
+    return torch.empty(nbytes, dtype=torch.uint8, device=rt.device)
+
+
+def pack_first9x9_bf16(rt, w, out=None):
+    """Conv2D (9,9,3,64) for vcg_conv9x9_from3_bf16_fwd[_train]"""
+    out = _bytes(rt, L.FIRST9X9_WFRAG_BYTES) if out is None else out
+    L.check(rt.lib.vcg_pack_first9x9_bf16(w.data_ptr(), out.data_ptr(), rt.stream), "vcg_pack_first9x9_bf16")
+    return out
+
+
+def pack_final9x9_bf16(rt, w, out=None):
+    """Conv2D (9,9,256,3) for vcg_conv9x9_to3_bf16_fwd"""
+    out = _bytes(rt, L.FINAL9X9_WFRAG_BYTES) if out is None else out
+    L.check(rt.lib.vcg_pack_final9x9_bf16(w.data_ptr(), out.data_ptr(), rt.stream), "vcg_pack_final9x9_bf16")
+    return out
+
+
+def pack_conv9x9_to3_bf16(rt, w, cin, out=None):
+    """Conv2D (9,9,cin,3) for vcg_conv9x9_to3_bf16_fwd on another channel count than 256"""
+    out = _bytes(rt, rt.lib.vcg_conv9x9_to3_bf16_wfrag_bytes(cin)) if out is None else out
+    L.check(rt.lib.vcg_pack_conv9x9_to3_bf16(w.data_ptr(), cin, out.data_ptr(), rt.stream), "vcg_pack_conv9x9_to3_bf16")
+    return out
+
+
+def pack_conv_kernel_bf16(rt, w, taps, a, b, transpose, flip, out=None):
+    """[tap][a][b] bf16 (include/vcg.h: vcg_pack_conv_kernel_bf16), what the 3x3 64-channel kernels read"""
+    out = _bf16(rt, taps, a, b) if out is None else out
+    L.check(rt.lib.vcg_pack_conv_kernel_bf16(w.data_ptr(), taps, a, b, transpose, flip, out.data_ptr(), rt.stream), "vcg_pack_conv_kernel_bf16")
+    return out
+
+
+def pack_conv_frag_bf16(rt, w, taps, mdim, kdim, mode, out=None):
+    """the generic kernels' MFMA fragments; mode 0: a Keras Conv2D kernel for its forward, 1: for its data gradient, 2: that with the taps
+    reversed (include/vcg.h: vcg_pack_conv_frag_bf16)"""
+    out = _bf16(rt, taps, mdim, kdim) if out is None else out
+    L.check(rt.lib.vcg_pack_conv_frag_bf16(w.data_ptr(), taps, mdim, kdim, mode, out.data_ptr(), rt.stream), "vcg_pack_conv_frag_bf16")
+    return out
+
+
+def pack_conv_frag_bf16_pair(rt, w, taps, cin, cout, out=None):
+    """modes 0 and 1 of a Keras (k,k,cin,cout) kernel in one launch -> (forward, data gradient)"""
+    wf, wd = (_bf16(rt, taps, cout, cin), _bf16(rt, taps, cin, cout)) if out is None else out
+    L.check(rt.lib.vcg_pack_conv_frag_bf16_pair(w.data_ptr(), taps, cin, cout, wf.data_ptr(), wd.data_ptr(), rt.stream), "vcg_pack_conv_frag_bf16_pair")
+    return wf, wd
+
+
+def pack_conv3ch_bf16(rt, w, kh, kw, cout, out=None):
+    """Conv2D (kh,kw,3,cout) for vcg_conv3ch_bf16_fwd"""
+    out = _bytes(rt, rt.lib.vcg_conv3ch_bf16_wfrag_bytes(kh, kw, cout)) if out is None else out
+    L.check(rt.lib.vcg_pack_conv3ch_bf16(w.data_ptr(), kh, kw, cout, out.data_ptr(), rt.stream), "vcg_pack_conv3ch_bf16")
+    return out
+
+
+def pack_conv_in_gate_bf16(rt, w, cin, kh, kw, cout):
+    """Conv2D (kh,kw,cin,cout) for vcg_conv_in_gate_bf16_fwd; None where that kernel does not serve the shape"""
+    nbytes = rt.lib.vcg_conv_in_gate_bf16_wfrag_bytes(cin, kh, kw, cout)
+    if nbytes == 0:
+        return None
+    out = _bytes(rt, nbytes)
+    L.check(rt.lib.vcg_pack_conv_in_gate_bf16(w.data_ptr(), cin, kh, kw, cout, out.data_ptr(), rt.stream), "vcg_pack_conv_in_gate_bf16")
+    return out
+
+
+class TrunkConvBf16(Conv2D):
+    """what the generator's 64 -> 64 'same' trunk convolutions on bf16 NHWC share (Conv3x3Bf16, Conv5x5Bf16): the learning-phase-0 forward
+    with the normalisation folded in and the data gradient, both on vcg_conv2d_bf16_fwd.  A subclass packs (forward, data gradient)
+    operands in _pack(out) and has its own training forward and weight gradient."""
+
+    def __init__(self, name, cin, cout, k):
         if cin != 64 or cout != 64:
-            raise NotImplementedError("the bf16 trunk convolution is instantiated for 64 -> 64 channels")
-        self.cin, self.cout, self.k = cin, cout, 3
-        self._wf = self._wd = None
-        self._valid = False
-        self._group = None              # PackGroup3x3: all of a model's 3x3 kernels re-packed in one launch
-
-    def declare(self, ps):
-        ps.declare(self.name + "/kernel", (3, 3, self.cin, self.cout))
-        ps.declare(self.name + "/bias", (self.cout,))
-
-    def init_weights(self, rng):
-        return {self.name + "/kernel": glorot_uniform(rng, (3, 3, self.cin, self.cout), 9 * self.cin, 9 * self.cout),
-                self.name + "/bias": np.zeros((self.cout,), np.float32)}
-
-    def refresh(self):
-        self._valid = False
-        if self._group is not None:
-            self._group.valid = False
-
-    def _packed(self):
-        rt = self.rt
-        if self._group is not None:
-            self._group.ensure()
-            return self._wf, self._wd
-        if self._wf is None:
-            self._wf = torch.empty(9, 64, 64, dtype=torch.bfloat16, device=rt.device)
-            self._wd = torch.empty(9, 64, 64, dtype=torch.bfloat16, device=rt.device)
-        if not self._valid:
-            w = self.ps[self.name + "/kernel"].data_ptr()
-            L.check(rt.lib.vcg_pack_conv_kernel_bf16(w, 9, 64, 64, 1, 0, self._wf.data_ptr(), rt.stream), "pack fwd")      # [tap][co][ci]
-            L.check(rt.lib.vcg_pack_conv_kernel_bf16(w, 9, 64, 64, 0, 1, self._wd.data_ptr(), rt.stream), "pack dgrad")    # [tap'][ci][co]
-            self._valid = True
-        return self._wf, self._wd
-
-    def _run(self, x, w, bias, residual=None, stats=None, stats_mode=L.STATS_NONE):
-        rt = self.rt
-        n, h, wd, _ = x.shape
-        y = torch.empty(n, h, wd, 64, dtype=torch.bfloat16, device=rt.device)
-        d = L.ConvDesc(n, 64, h, wd, 64, h, wd, 3, 3, 1, 1, 1)
-        ep = L.EpilogueBf16(None, bias, L.ACT_NONE, 0.0, None, _ptr(residual), _ptr(stats), stats_mode if stats is not None else L.STATS_NONE)
-        L.check(rt.lib.vcg_conv2d_bf16_fwd(ctypes.byref(d), x.data_ptr(), w.data_ptr(), y.data_ptr(), ctypes.byref(ep), rt.stream),
-                "vcg_conv2d_bf16_fwd[%s]" % self.name)
-        return y, d
-
-    def forward(self, x, tag=None):
-        wf, _ = self._packed()
-        with Timed(self.rt, tag):
-            y, d = self._run(x, wf, self.ps[self.name + "/bias"].data_ptr())
-        return y, (x, d)
+            raise NotImplementedError("the bf16 %dx%d trunk convolution is instantiated for 64 -> 64 channels" % (k, k))
+        super().__init__(name, cin, cout, k)
+        self._pk = PackedOperand(self._pack, self)
 
     def forward_folded(self, x, norm, residual=None, tag=None, folded=None):
         """learning phase 0: conv + BatchNormalization (moving statistics) [+ PReLU] [+ Add] in ONE launch -- the normalisation is an
         affine map per channel, folded with the bias into the epilogue's scale / shift (vcg_bn_fold); the pre-normalisation tensor is
         never stored.  norm: the NormActBf16 behind this convolution (batch norm).  folded: (scale, shift) already derived (fold_batch)."""
         rt, ps = self.rt, self.ps
-        n, h, wd, _ = x.shape
+        n, h, w, _ = x.shape
         if folded is not None:
             scale, shift = folded
         else:
@@ -703,32 +733,71 @@ class Conv3x3Bf16(Layer):
             L.check(rt.lib.vcg_bn_fold(ps[self.name + "/bias"].data_ptr(), ps[norm.name + "/moving_mean"].data_ptr(),
                                        ps[norm.name + "/moving_variance"].data_ptr(), ps[norm.name + "/gamma"].data_ptr(),
                                        ps[norm.name + "/beta"].data_ptr(), 64, BN_EPS, scale.data_ptr(), shift.data_ptr(), rt.stream), "vcg_bn_fold")
-        wf, _ = self._packed()
-        y = torch.empty(n, h, wd, 64, dtype=torch.bfloat16, device=rt.device)
-        d = L.ConvDesc(n, 64, h, wd, 64, h, wd, 3, 3, 1, 1, 1)
+        wf, _ = self._pk.get()
+        y = _bf16(rt, n, h, w, 64)
+        d = self.desc(n, h, w)
         ep = L.EpilogueBf16(scale.data_ptr(), shift.data_ptr(), norm.act, float(norm.alpha), norm._alpha_ptr(), _ptr(residual), None, L.STATS_NONE)
         with Timed(rt, tag and residual is not None and tag + "_res" or tag):
             L.check(rt.lib.vcg_conv2d_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), y.data_ptr(), ctypes.byref(ep), rt.stream),
                     "vcg_conv2d_bf16_fwd[%s]" % self.name)
         return y
 
+    def _dgrad(self, d, dy, dx_residual, tag):
+        """dx = the same convolution over dy with the data-gradient pack; dx_residual (a gradient joining at the layer's input) is the
+        epilogue's residual operand, added in fp32 before the one rounding to bf16"""
+        rt = self.rt
+        _, wd = self._pk.get()
+        dx = _bf16(rt, d.n, d.h, d.w, 64)
+        ep = L.EpilogueBf16(None, None, L.ACT_NONE, 0.0, None, _ptr(dx_residual), None, L.STATS_NONE)
+        with Timed(rt, tag and tag + ("_dgrad_res" if dx_residual is not None else "_dgrad")):
+            L.check(rt.lib.vcg_conv2d_bf16_fwd(ctypes.byref(d), dy.data_ptr(), wd.data_ptr(), dx.data_ptr(), ctypes.byref(ep), rt.stream),
+                    "vcg_conv2d_bf16_fwd[%s dgrad]" % self.name)
+        return dx
+
+
+class Conv3x3Bf16(TrunkConvBf16):
+    """Conv2D(64, 3, 'same') on bf16 NHWC: forward and data gradient on vcg_conv2d_bf16_fwd (the latter with the kernel
+    packed tap-flipped and transposed), weight / bias gradient on vcg_conv2d_bf16_wgrad (fp32, into the master gradient)."""
+
+    def __init__(self, name, cin=64, cout=64):
+        super().__init__(name, cin, cout, 3)
+
+    def _pack(self, out):
+        w = self.ps[self.name + "/kernel"]
+        wf, wd = out or (None, None)
+        return (pack_conv_kernel_bf16(self.rt, w, 9, 64, 64, 1, 0, wf),       # [tap][co][ci]
+                pack_conv_kernel_bf16(self.rt, w, 9, 64, 64, 0, 1, wd))       # [tap'][ci][co]
+
+    def _run(self, x, d, tag, stats=None, stats_mode=L.STATS_NONE):
+        """y = conv(x) + bias [+ the statistics partials of y]"""
+        rt = self.rt
+        wf, _ = self._pk.get()
+        y = _bf16(rt, d.n, d.h, d.w, 64)
+        ep = L.EpilogueBf16(None, self.ps[self.name + "/bias"].data_ptr(), L.ACT_NONE, 0.0, None, None, _ptr(stats), stats_mode)
+        with Timed(rt, tag):
+            L.check(rt.lib.vcg_conv2d_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), y.data_ptr(), ctypes.byref(ep), rt.stream),
+                    "vcg_conv2d_bf16_fwd[%s]" % self.name)
+        return y
+
+    def forward(self, x, tag=None):
+        n, h, w, _ = x.shape
+        d = self.desc(n, h, w)
+        return self._run(x, d, tag), (x, d)
+
     def forward_stats(self, x, instance, tag=None):
         """forward that also leaves the statistics partials of its output for the normalisation behind it (model.py:20,23,284 in
         training mode): returns (y, ctx, stats) with stats = (records buffer, records per group) or None when the kernel serving
         this shape has no statistics epilogue (the caller then runs the separate statistics pass)"""
         rt = self.rt
-        n, h, wd, _ = x.shape
+        n, h, w, _ = x.shape
         mode = L.STATS_INSTANCE if instance else L.STATS_BATCH
-        d = L.ConvDesc(n, 64, h, wd, 64, h, wd, 3, 3, 1, 1, 1)
+        d = self.desc(n, h, w)
         nrec = rt.lib.vcg_conv2d_bf16_stats_records(ctypes.byref(d), mode)
         if nrec <= 0:
             y, ctx = self.forward(x, tag)
             return y, ctx, None
         buf = rt.empty((n if instance else 1) * nrec * 2 * 64)
-        wf, _ = self._packed()
-        with Timed(rt, tag):
-            y, d = self._run(x, wf, self.ps[self.name + "/bias"].data_ptr(), None, buf, mode)
-        return y, (x, d), (buf, nrec)
+        return self._run(x, d, tag, buf, mode), (x, d), (buf, nrec)
 
     def backward(self, ctx, dy, need_dx=True, param_grads=True, which=0, dx_residual=None, tag=None):
         """dx_residual: a gradient that joins at this layer's input (the block's skip branch), added in the epilogue"""
@@ -740,12 +809,7 @@ class Conv3x3Bf16(Layer):
                 L.check(rt.lib.vcg_conv2d_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dy.data_ptr(), self.ps.grad(self.name + "/kernel", which).data_ptr(),
                                                      self.ps.grad(self.name + "/bias", which).data_ptr(), ws, wsn, rt.stream),
                         "vcg_conv2d_bf16_wgrad[%s]" % self.name)
-        if not need_dx:
-            return None
-        _, wdg = self._packed()
-        with Timed(rt, tag and tag + ("_dgrad_res" if dx_residual is not None else "_dgrad")):
-            dx, _ = self._run(dy, wdg, None, dx_residual)
-        return dx
+        return self._dgrad(d, dy, dx_residual, tag) if need_dx else None
 
 
 class PackGroup3x3:
@@ -755,23 +819,23 @@ class PackGroup3x3:
 
     def __init__(self, layers):
         self.layers = list(layers)
-        self.valid = False
-        self.buf = None
-        for l in self.layers:
-            l._group = self
+        self.all = PackedOperand(self._pack_all, *self.layers)          # stale as soon as any member is refreshed
+        for i, l in enumerate(self.layers):
+            # the member's own operand: its slices of the group's buffer, valid once the group is packed
+            l.caches.remove(l._pk)
+            l._pk = PackedOperand(lambda views, i=i: self._member(i, views), l)
 
-    def ensure(self):
-        if self.valid:
-            return
+    def _member(self, i, views):
+        buf = self.all.get()
+        return views or (buf[i, 0], buf[i, 1])
+
+    def _pack_all(self, buf):
         rt = self.layers[0].rt
         n = len(self.layers)
-        if self.buf is None:
-            self.buf = torch.empty(n, 2, 9, 64, 64, dtype=torch.bfloat16, device=rt.device)
-            for i, l in enumerate(self.layers):
-                l._wf, l._wd = self.buf[i, 0], self.buf[i, 1]
+        buf = _bf16(rt, n, 2, 9, 64, 64) if buf is None else buf
         arr = (ctypes.c_void_p * n)(*[l.ps[l.name + "/kernel"].data_ptr() for l in self.layers])
-        L.check(rt.lib.vcg_pack_conv3x3_c64_bf16_batch(arr, n, self.buf.data_ptr(), rt.stream), "vcg_pack_conv3x3_c64_bf16_batch")
-        self.valid = True
+        L.check(rt.lib.vcg_pack_conv3x3_c64_bf16_batch(arr, n, buf.data_ptr(), rt.stream), "vcg_pack_conv3x3_c64_bf16_batch")
+        return buf
 
 
 def fold_batch(rt, pairs):
@@ -802,30 +866,13 @@ class Conv2DBf16(Conv2D):
             # (bf16_gwgrad.hip: gw_plan) serves 3x3 / 4x4, stride 1 / 2, channel multiples of 64 -- a layer is built only if it can train
             raise NotImplementedError("Conv2DBf16 serves 3x3 / 4x4 kernels, stride 1 / 2, channel counts that are multiples of 64")
         super().__init__(name, cin, cout, k, stride, padding, act, alpha)
-        self._wf = self._wd = None
-        self._pvalid = False
-
-    def refresh(self):
-        super().refresh()
-        self._pvalid = False
-
-    def _packed(self):
-        rt = self.rt
-        t = self.k * self.k
-        if self._wf is None:
-            self._wf = torch.empty(t * self.cin * self.cout, dtype=torch.bfloat16, device=rt.device)
-            self._wd = torch.empty(t * self.cin * self.cout, dtype=torch.bfloat16, device=rt.device)
-        if not self._pvalid:
-            w = self.ps[self.name + "/kernel"].data_ptr()
-            L.check(rt.lib.vcg_pack_conv_frag_bf16_pair(w, t, self.cin, self.cout, self._wf.data_ptr(), self._wd.data_ptr(), rt.stream), "pack fwd + dgrad")
-            self._pvalid = True
-        return self._wf, self._wd
+        self._pk = PackedOperand(lambda out: pack_conv_frag_bf16_pair(self.rt, self.ps[self.name + "/kernel"], k * k, cin, cout, out), self)
 
     def forward(self, x, residual=None, tag=None):
         rt = self.rt
         n, h, w, _ = x.shape
         d = self.desc(n, h, w)
-        wf, _ = self._packed()
+        wf, _ = self._pk.get()
         y = torch.empty(n, d.oh, d.ow, self.cout, dtype=torch.bfloat16, device=rt.device)
         with Timed(rt, tag):
             L.check(rt.lib.vcg_conv2d_nhwc_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
@@ -842,7 +889,7 @@ class Conv2DBf16(Conv2D):
         if nrec <= 0:
             y, ctx = self.forward(x, tag=tag)
             return y, ctx, None
-        wf, _ = self._packed()
+        wf, _ = self._pk.get()
         y = torch.empty(n, d.oh, d.ow, self.cout, dtype=torch.bfloat16, device=rt.device)
         buf = rt.empty((n if instance else 1) * nrec * 2 * self.cout)
         with Timed(rt, tag):
@@ -864,7 +911,7 @@ class Conv2DBf16(Conv2D):
                         "vcg_conv2d_nhwc_bf16_wgrad[%s]" % self.name)
         if not need_dx:
             return None
-        _, wd = self._packed()
+        _, wd = self._pk.get()
         dx = torch.empty_like(x)
         with Timed(rt, tag and tag + "_dgrad"):
             L.check(rt.lib.vcg_conv2d_nhwc_bf16_dgrad(ctypes.byref(d), dy.data_ptr(), wd.data_ptr(),
@@ -873,7 +920,7 @@ class Conv2DBf16(Conv2D):
         return dx
 
 
-class Conv5x5Bf16(Conv2D):
+class Conv5x5Bf16(TrunkConvBf16):
     """Conv2D(64, 5, 'same') on bf16 NHWC, 64 -> 64: the trunk convolution of the reference's default generator (kernel_size=5,
     model.py:267) with the interface UpscalerOrig uses on Conv3x3Bf16.  Training forward on vcg_conv2d_nhwc_bf16_fwd[_stats] (the
     statistics partials of the normalisation behind it out of the epilogue), learning phase 0 on vcg_conv2d_bf16_fwd's 5x5 form with the
@@ -883,58 +930,23 @@ class Conv5x5Bf16(Conv2D):
     tap groups per block pair)."""
 
     def __init__(self, name, cin=64, cout=64):
-        if cin != 64 or cout != 64:
-            raise NotImplementedError("the bf16 5x5 trunk convolution is instantiated for 64 -> 64 channels")
         super().__init__(name, cin, cout, 5)
-        self._wf = self._wd = None
-        self._pvalid = False
 
-    def refresh(self):
-        super().refresh()
-        self._pvalid = False
-
-    def _packed(self):
-        rt = self.rt
-        if self._wf is None:
-            self._wf = torch.empty(25 * 64 * 64, dtype=torch.bfloat16, device=rt.device)
-            self._wd = torch.empty(25 * 64 * 64, dtype=torch.bfloat16, device=rt.device)
-        if not self._pvalid:
-            w = self.ps[self.name + "/kernel"].data_ptr()
-            L.check(rt.lib.vcg_pack_conv_frag_bf16(w, 25, 64, 64, 0, self._wf.data_ptr(), rt.stream), "pack fwd")
-            L.check(rt.lib.vcg_pack_conv_frag_bf16(w, 25, 64, 64, 2, self._wd.data_ptr(), rt.stream), "pack dgrad")
-            self._pvalid = True
-        return self._wf, self._wd
+    def _pack(self, out):
+        w = self.ps[self.name + "/kernel"]
+        wf, wd = out or (None, None)
+        return pack_conv_frag_bf16(self.rt, w, 25, 64, 64, 0, wf), pack_conv_frag_bf16(self.rt, w, 25, 64, 64, 2, wd)
 
     def forward(self, x, tag=None):
         rt = self.rt
         n, h, w, _ = x.shape
         d = self.desc(n, h, w)
-        wf, _ = self._packed()
+        wf, _ = self._pk.get()
         y = torch.empty(n, h, w, 64, dtype=torch.bfloat16, device=rt.device)
         with Timed(rt, tag):
             L.check(rt.lib.vcg_conv2d_nhwc_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
                                                     L.ACT_NONE, 0.0, y.data_ptr(), rt.stream), "vcg_conv2d_nhwc_bf16_fwd[%s]" % self.name)
         return y, (x, d)
-
-    def forward_folded(self, x, norm, residual=None, tag=None, folded=None):
-        """learning phase 0: conv + BatchNormalization (moving statistics) [+ PReLU] [+ Add] in one launch (see Conv3x3Bf16.forward_folded)"""
-        rt, ps = self.rt, self.ps
-        n, h, w, _ = x.shape
-        if folded is not None:
-            scale, shift = folded
-        else:
-            scale, shift = rt.empty(64), rt.empty(64)
-            L.check(rt.lib.vcg_bn_fold(ps[self.name + "/bias"].data_ptr(), ps[norm.name + "/moving_mean"].data_ptr(),
-                                       ps[norm.name + "/moving_variance"].data_ptr(), ps[norm.name + "/gamma"].data_ptr(),
-                                       ps[norm.name + "/beta"].data_ptr(), 64, BN_EPS, scale.data_ptr(), shift.data_ptr(), rt.stream), "vcg_bn_fold")
-        wf, _ = self._packed()
-        y = torch.empty(n, h, w, 64, dtype=torch.bfloat16, device=rt.device)
-        d = self.desc(n, h, w)
-        ep = L.EpilogueBf16(scale.data_ptr(), shift.data_ptr(), norm.act, float(norm.alpha), norm._alpha_ptr(), _ptr(residual), None, L.STATS_NONE)
-        with Timed(rt, tag and residual is not None and tag + "_res" or tag):
-            L.check(rt.lib.vcg_conv2d_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), y.data_ptr(), ctypes.byref(ep), rt.stream),
-                    "vcg_conv2d_bf16_fwd[%s]" % self.name)
-        return y
 
     def forward_stats(self, x, instance, tag=None):
         """forward + per-tile statistics partials of the output (see Conv3x3Bf16.forward_stats); None where the tiled kernel does not
@@ -946,7 +958,7 @@ class Conv5x5Bf16(Conv2D):
         if nrec <= 0:
             y, ctx = self.forward(x, tag)
             return y, ctx, None
-        wf, _ = self._packed()
+        wf, _ = self._pk.get()
         y = torch.empty(n, h, w, 64, dtype=torch.bfloat16, device=rt.device)
         buf = rt.empty((n if instance else 1) * nrec * 2 * 64)
         with Timed(rt, tag):
@@ -965,15 +977,7 @@ class Conv5x5Bf16(Conv2D):
                                                           self.ps.grad(self.name + "/kernel", which).data_ptr(),
                                                           self.ps.grad(self.name + "/bias", which).data_ptr(), ws, wsn, rt.stream),
                         "vcg_conv2d_nhwc_bf16_wgrad[%s]" % self.name)
-        if not need_dx:
-            return None
-        _, wd = self._packed()
-        dx = torch.empty_like(x)
-        ep = L.EpilogueBf16(None, None, L.ACT_NONE, 0.0, None, _ptr(dx_residual), None, L.STATS_NONE)
-        with Timed(rt, tag and tag + ("_dgrad_res" if dx_residual is not None else "_dgrad")):
-            L.check(rt.lib.vcg_conv2d_bf16_fwd(ctypes.byref(d), dy.data_ptr(), wd.data_ptr(), dx.data_ptr(), ctypes.byref(ep), rt.stream),
-                    "vcg_conv2d_bf16_fwd[%s dgrad]" % self.name)
-        return dx
+        return self._dgrad(d, dy, dx_residual, tag) if need_dx else None
 
 
 class InitialConv9x9Bf16(Conv2D):
@@ -988,28 +992,14 @@ class InitialConv9x9Bf16(Conv2D):
         if cin != 3 or cout != 64 or k != 9:
             raise NotImplementedError("the bf16 initial convolution is instantiated for 9x9, 3 -> 64 channels")
         super().__init__(name, cin, cout, k)
-        self._wf = None
-        self._pvalid = False
-
-    def refresh(self):
-        super().refresh()
-        self._pvalid = False
-
-    def _packed(self):
-        rt = self.rt
-        if self._wf is None:
-            self._wf = torch.empty(L.FIRST9X9_WFRAG_BYTES, dtype=torch.uint8, device=rt.device)
-        if not self._pvalid:
-            L.check(rt.lib.vcg_pack_first9x9_bf16(self.ps[self.name + "/kernel"].data_ptr(), self._wf.data_ptr(), rt.stream), "vcg_pack_first9x9_bf16")
-            self._pvalid = True
-        return self._wf
+        self._pk = PackedOperand(lambda out: pack_first9x9_bf16(self.rt, self.ps[self.name + "/kernel"], out), self)
 
     def forward_prelu(self, x, alpha, training, tag=None):
         """x fp32 NCHW frames, alpha: the PReLU slopes [64] -> (y bf16 NHWC, ctx)"""
         rt = self.rt
         n, _, h, w = x.shape
         d = self.desc(n, h, w)
-        wf = self._packed()
+        wf = self._pk.get()
         y = torch.empty(n, h, w, self.cout, dtype=torch.bfloat16, device=rt.device)
         bias = self.ps[self.name + "/bias"].data_ptr()
         with Timed(rt, tag):
@@ -1051,10 +1041,7 @@ class InitialConv9x9Bf16(Conv2D):
         L.check(lib.vcg_prelu_bwd_nhwc_bf16(d1.data_ptr(), _ptr(d2), z.data_ptr(), alpha.data_ptr(), d.n, self.cout, hw, dz.data_ptr(),
                                             rec.data_ptr(), rt.stream), "vcg_prelu_bwd_nhwc_bf16")
         L.check(lib.vcg_sum_records(rec.data_ptr(), nrec, self.cout, 1.0, dalpha.data_ptr(), rt.stream), "vcg_sum_records[%s]" % self.name)
-        ws, wsn = rt.workspace(lib.vcg_conv2d_wgrad_workspace_bytes(ctypes.byref(d)))
-        with Timed(rt, tag and tag + "_wgrad"):
-            L.check(lib.vcg_conv2d_wgrad(ctypes.byref(d), x.data_ptr(), dz.data_ptr(), gk.data_ptr(), gb.data_ptr(), ws, wsn, rt.stream),
-                    "vcg_conv2d_wgrad[%s]" % self.name)
+        self._wgrad_fp32(d, x, dz, which, True, tag)
 
 
 class FirstConvBf16(Conv2D):
@@ -1068,28 +1055,14 @@ class FirstConvBf16(Conv2D):
         if cin != 3 or cout % 64 or cout > 512 or (k, stride) not in ((3, 1), (4, 2)) or act not in (L.ACT_NONE, L.ACT_LRELU):
             raise NotImplementedError("FirstConvBf16 serves Conv2D(64m, 3, strides 1) / Conv2D(64m, 4, strides 2) on 3 input channels")
         super().__init__(name, cin, cout, k, stride, padding, act, alpha)
-        self._wf = None
-        self._pvalid = False
-
-    def refresh(self):
-        super().refresh()
-        self._pvalid = False
-
-    def _packed(self):
-        rt = self.rt
-        if self._wf is None:
-            self._wf = torch.empty(rt.lib.vcg_conv3ch_bf16_wfrag_bytes(self.kh, self.kw, self.cout), dtype=torch.uint8, device=rt.device)
-        if not self._pvalid:
-            L.check(rt.lib.vcg_pack_conv3ch_bf16(self.ps[self.name + "/kernel"].data_ptr(), self.kh, self.kw, self.cout, self._wf.data_ptr(), rt.stream),
-                    "vcg_pack_conv3ch_bf16")
-            self._pvalid = True
-        return self._wf
+        # next to Conv2D's _wt, which only the fp32 data-gradient fallback of backward asks for
+        self._pk = PackedOperand(lambda out: pack_conv3ch_bf16(self.rt, self.ps[self.name + "/kernel"], k, k, cout, out), self)
 
     def forward(self, x, residual=None, tag=None):
         rt = self.rt
         n, _, h, w = x.shape
         d = self.desc(n, h, w)
-        wf = self._packed()
+        wf = self._pk.get()
         y = torch.empty(n, d.oh, d.ow, self.cout, dtype=torch.bfloat16, device=rt.device)
         with Timed(rt, tag):
             L.check(rt.lib.vcg_conv3ch_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
@@ -1112,10 +1085,7 @@ class FirstConvBf16(Conv2D):
                             "vcg_conv3ch_bf16_wgrad[%s]" % self.name)
             else:       # odd widths: the fp32 weight-gradient kernel on an fp32 NCHW copy of dz
                 dz32 = from_bf16_nhwc(rt, dz)
-                ws, wsn = rt.workspace(rt.lib.vcg_conv2d_wgrad_workspace_bytes(ctypes.byref(d)))
-                with Timed(rt, tag and tag + "_wgrad"):
-                    L.check(rt.lib.vcg_conv2d_wgrad(ctypes.byref(d), x.data_ptr(), dz32.data_ptr(), gk.data_ptr(), gb.data_ptr(), ws, wsn, rt.stream),
-                            "vcg_conv2d_wgrad[%s]" % self.name)
+                self._wgrad_fp32(d, x, dz32, which, True, tag)
         if not need_dx:
             return None
         dx = rt.empty(d.n, self.cin, d.h, d.w)
@@ -1125,7 +1095,7 @@ class FirstConvBf16(Conv2D):
             rc = rt.lib.vcg_conv3ch_bf16_dgrad(ctypes.byref(d), dz.data_ptr(), self.ps[self.name + "/kernel"].data_ptr(), dx.data_ptr(), ws, wsn, rt.stream)
             if rc == L.E_UNSUPPORTED:       # other pads / channel counts: the fp32 data-gradient kernel on the fp32 copy of dz
                 dz32 = from_bf16_nhwc(rt, dz) if dz32 is None else dz32
-                rc = rt.lib.vcg_conv2d_dgrad(ctypes.byref(d), dz32.data_ptr(), self.ps[self.name + "/kernel"].data_ptr(), self._wt().data_ptr(),
+                rc = rt.lib.vcg_conv2d_dgrad(ctypes.byref(d), dz32.data_ptr(), self.ps[self.name + "/kernel"].data_ptr(), self._wt.get().data_ptr(),
                                              dx.data_ptr(), None, rt.stream)
             L.check(rc, "vcg_conv3ch_bf16_dgrad[%s]" % self.name)
         return dx
@@ -1184,122 +1154,34 @@ def f32_to_bf16(rt, x):
     return y
 
 
-class ConvT3x3Bf16(ConvT2D):
-    """upsampling_block (model.py:70-75) with bf16 activations: Conv2DTranspose(3, strides 2) 64 -> 64m + bias + LeakyReLU forward on
-    vcg_conv_transpose2d_bf16_fwd (bf16 NHWC in and out).  Backward takes the gradient dz in front of the activation (the bf16 data
-    gradient of final/conv applies the LeakyReLU derivative itself): data gradient = the stride-2 convolution of dz with the kernel
-    read as (in = out-channels, out = in-channels) on vcg_conv2d_nhwc_bf16_fwd, weight gradient on
-    vcg_conv_transpose2d_nhwc_bf16_wgrad, bias gradient = per-channel sum of dz (vcg_norm_stats_bf16's shifted sums)."""
-
-    def __init__(self, name, cin, cout, k, act=L.ACT_NONE, alpha=0.0):
-        if k != 3 or cin != 64 or cout % 64:
-            raise NotImplementedError("the bf16 transposed convolution is instantiated for 3x3, 64 -> 64m channels")
-        super().__init__(name, cin, cout, k, act, alpha)
-        self._wp = self._wg = None
-        self._pvalid = False
-
-    def refresh(self):
-        super().refresh()
-        self._pvalid = False
-
-    def _packed(self):
-        rt = self.rt
-        if self._wp is None:
-            self._wp = torch.empty(9, self.cout, self.cin, dtype=torch.bfloat16, device=rt.device)
-            self._wg = torch.empty(9 * self.cout * self.cin, dtype=torch.bfloat16, device=rt.device)
-        if not self._pvalid:
-            w = self.ps[self.name + "/kernel"]
-            L.check(rt.lib.vcg_pack_conv_kernel_bf16(w.data_ptr(), 9, self.cout, self.cin, 0, 0, self._wp.data_ptr(), rt.stream), "pack convT")
-            # data gradient: Keras' (kh,kw,out,in) kernel is a Conv2D kernel (kh,kw,in'=out,out'=in) of the convolution dz -> dx
-            L.check(rt.lib.vcg_pack_conv_frag_bf16(w.data_ptr(), 9, self.cin, self.cout, 0, self._wg.data_ptr(), rt.stream), "pack convT dgrad")
-            self._pvalid = True
-        return self._wp, self._wg
-
-    def forward(self, x, tag=None):
-        rt = self.rt
-        n, h, w, _ = x.shape
-        wp, _ = self._packed()
-        y = torch.empty(n, 2 * h, 2 * w, self.cout, dtype=torch.bfloat16, device=rt.device)
-        d = self.desc(n, h, w)
-        ep = L.EpilogueBf16(None, self.ps[self.name + "/bias"].data_ptr(), self.act, float(self.alpha), None, None)
-        with Timed(rt, tag):
-            L.check(rt.lib.vcg_conv_transpose2d_bf16_fwd(ctypes.byref(d), x.data_ptr(), wp.data_ptr(), y.data_ptr(), ctypes.byref(ep), rt.stream),
-                    "vcg_conv_transpose2d_bf16_fwd[%s]" % self.name)
-        return y, (x, y, d)
-
-    def backward(self, ctx, dz, need_dx=True, param_grads=True, which=0, tag=None, dz_channel_sums=None):
-        """dz: bf16 NHWC gradient in front of the LeakyReLU.  Returns dx as bf16 NHWC.  dz_channel_sums: (records, count) left by the
-        kernel that produced dz (FinalConv9x9Bf16.backward) -- the bias gradient then needs no pass over dz."""
-        rt, lib = self.rt, self.rt.lib
-        x, _, d = ctx
-        _, wg = self._packed()
-        if param_grads:
-            ws, wsn = rt.workspace(lib.vcg_conv_transpose2d_nhwc_bf16_wgrad_workspace_bytes(ctypes.byref(d)))
-            with Timed(rt, tag and tag + "_wgrad"):
-                L.check(lib.vcg_conv_transpose2d_nhwc_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dz.data_ptr(),
-                                                                 self.ps.grad(self.name + "/kernel", which).data_ptr(), ws, wsn, rt.stream),
-                        "vcg_conv_transpose2d_nhwc_bf16_wgrad[%s]" % self.name)
-            # bias gradient: sum of dz over (n, h, w)
-            if dz_channel_sums is not None:
-                rec, nrec = dz_channel_sums
-                L.check(lib.vcg_sum_records(rec.data_ptr(), nrec, self.cout, 1.0, self.ps.grad(self.name + "/bias", which).data_ptr(), rt.stream),
-                        "vcg_sum_records[%s]" % self.name)
-        if param_grads and dz_channel_sums is None:
-            # ... = its per-channel mean x count (the shifted sums of vcg_norm_stats_bf16)
-            hw = d.oh * d.ow
-            mean, var = rt.empty(self.cout), rt.empty(self.cout)
-            ws, wsn = rt.workspace(lib.vcg_norm_stats_bf16_workspace_bytes(d.n, self.cout, hw, L.NORM_BATCH))
-            L.check(lib.vcg_norm_stats_bf16(dz.data_ptr(), d.n, self.cout, hw, L.NORM_BATCH, mean.data_ptr(), var.data_ptr(), ws, wsn, rt.stream),
-                    "vcg_norm_stats_bf16[%s]" % self.name)
-            axpby(rt, mean, self.ps.grad(self.name + "/bias", which), float(d.n * hw), 0.0)
-        if not need_dx:
-            return None
-        # dx[ci][i] = sum dz[co][2i + k - crop] W[k][co][ci]: a stride-2 convolution over dz (pad = the crop)
-        dd = L.ConvDesc(d.n, self.cout, d.oh, d.ow, self.cin, d.h, d.w, self.k, self.k, 2, d.pad_top, d.pad_left)
-        dx = torch.empty_like(x)
-        with Timed(rt, tag and tag + "_dgrad"):
-            L.check(lib.vcg_conv2d_nhwc_bf16_fwd(ctypes.byref(dd), dz.data_ptr(), wg.data_ptr(), None, L.ACT_NONE, 0.0, dx.data_ptr(), rt.stream),
-                    "vcg_conv2d_nhwc_bf16_fwd[%s dgrad]" % self.name)
-        return dx
-
-
 class ConvTBf16(ConvT2D):
-    """upsampling_block (model.py:70-75) on bf16 NHWC beyond the k3 x2 topology: Conv2DTranspose(k, strides 2) + bias + LeakyReLU for k in
-    {3, 5}, 64 or 256 input channels (the first and the later stages of an x4 generator), out-channels a multiple of 64.  Forward on
-    vcg_conv_transpose2d_nhwc_bf16_fwd.  Backward takes the gradient dz in front of the layer's own activation; weight gradient on
-    vcg_conv_transpose2d_nhwc_bf16_wgrad, bias gradient = per-channel sum of dz, data gradient = the stride-2 convolution over dz
-    (vcg_conv2d_nhwc_bf16_fwd), as ConvT3x3Bf16 does them."""
+    """upsampling_block (model.py:70-75) on bf16 NHWC: Conv2DTranspose(k, strides 2) + bias + LeakyReLU for k in {3, 5}, 64 or 256 input
+    channels (the first and the later stages of an x4 generator), out-channels a multiple of 64.  Forward on
+    vcg_conv_transpose2d_nhwc_bf16_fwd.  Backward takes the gradient dz in front of the layer's own activation (the bf16 data gradient of
+    final/conv applies the LeakyReLU derivative itself): weight gradient on vcg_conv_transpose2d_nhwc_bf16_wgrad, bias gradient =
+    per-channel sum of dz (from the producer's records, or vcg_norm_stats_bf16's shifted sums), data gradient = the stride-2 convolution
+    of dz with the kernel read as (in = out-channels, out = in-channels) on vcg_conv2d_nhwc_bf16_fwd."""
 
     def __init__(self, name, cin, cout, k, act=L.ACT_NONE, alpha=0.0):
         if k not in (3, 5) or cin not in (64, 256) or cout % 64 or cout <= 0 or act not in (L.ACT_NONE, L.ACT_LRELU):
             raise NotImplementedError("the generic bf16 transposed convolution serves 3x3 / 5x5, 64 or 256 -> 64m channels, no activation or LeakyReLU")
         super().__init__(name, cin, cout, k, act, alpha)
-        self._wp = self._wg = None
-        self._pvalid = False
+        self._pk = PackedOperand(self._pack, self)
 
-    def refresh(self):
-        super().refresh()
-        self._pvalid = False
+    def _pack(self, out):
+        # Keras' (kh,kw,out,in) kernel is the Conv2D kernel (kh,kw,in'=out,out'=in) of the stride-2 convolution dz -> dx: the forward
+        # is that convolution's data gradient (mode 1), the layer's data gradient its forward (mode 0)
+        w = self.ps[self.name + "/kernel"]
+        wp, wg = out or (None, None)
+        return self._pack_fwd(w, wp), pack_conv_frag_bf16(self.rt, w, self.k * self.k, self.cin, self.cout, 0, wg)
 
-    def _packed(self):
-        rt = self.rt
-        t = self.k * self.k
-        if self._wp is None:
-            self._wp = torch.empty(t * self.cout * self.cin, dtype=torch.bfloat16, device=rt.device)
-            self._wg = torch.empty(t * self.cout * self.cin, dtype=torch.bfloat16, device=rt.device)
-        if not self._pvalid:
-            w = self.ps[self.name + "/kernel"].data_ptr()
-            # Keras' (kh,kw,out,in) kernel is the Conv2D kernel (kh,kw,in'=out,out'=in) of the stride-2 convolution dz -> dx: the forward
-            # is that convolution's data gradient (mode 1), the layer's data gradient its forward (mode 0)
-            L.check(rt.lib.vcg_pack_conv_frag_bf16(w, t, self.cout, self.cin, 1, self._wp.data_ptr(), rt.stream), "pack convT")
-            L.check(rt.lib.vcg_pack_conv_frag_bf16(w, t, self.cin, self.cout, 0, self._wg.data_ptr(), rt.stream), "pack convT dgrad")
-            self._pvalid = True
-        return self._wp, self._wg
+    def _pack_fwd(self, w, out):
+        return pack_conv_frag_bf16(self.rt, w, self.k * self.k, self.cout, self.cin, 1, out)
 
     def forward(self, x, tag=None):
         rt = self.rt
         n, h, w, _ = x.shape
-        wp, _ = self._packed()
+        wp, _ = self._pk.get()
         y = torch.empty(n, 2 * h, 2 * w, self.cout, dtype=torch.bfloat16, device=rt.device)
         d = self.desc(n, h, w)
         with Timed(rt, tag):
@@ -1314,7 +1196,7 @@ class ConvTBf16(ConvT2D):
         (the up-sampling stage below); dx is then multiplied by its derivative (vcg_lrelu_bwd_bf16), i.e. it is that stage's dz."""
         rt, lib = self.rt, self.rt.lib
         x, _, d = ctx
-        _, wg = self._packed()
+        _, wg = self._pk.get()
         if param_grads:
             ws, wsn = rt.workspace(lib.vcg_conv_transpose2d_nhwc_bf16_wgrad_workspace_bytes(ctypes.byref(d)))
             with Timed(rt, tag and tag + "_wgrad"):
@@ -1347,6 +1229,31 @@ class ConvTBf16(ConvT2D):
         return dx
 
 
+class ConvT3x3Bf16(ConvTBf16):
+    """The up-sampling stage of the k3 x2 topology, Conv2DTranspose(3, strides 2) 64 -> 64m + bias + LeakyReLU: a ConvTBf16 whose forward
+    runs on the kernel built for this shape, vcg_conv_transpose2d_bf16_fwd, reading the kernel as [tap][out][in] bf16."""
+
+    def __init__(self, name, cin, cout, k, act=L.ACT_NONE, alpha=0.0):
+        if k != 3 or cin != 64 or cout % 64:
+            raise NotImplementedError("the bf16 transposed convolution is instantiated for 3x3, 64 -> 64m channels")
+        super().__init__(name, cin, cout, k, act, alpha)
+
+    def _pack_fwd(self, w, out):
+        return pack_conv_kernel_bf16(self.rt, w, 9, self.cout, self.cin, 0, 0, out)
+
+    def forward(self, x, tag=None):
+        rt = self.rt
+        n, h, w, _ = x.shape
+        wp, _ = self._pk.get()
+        y = _bf16(rt, n, 2 * h, 2 * w, self.cout)
+        d = self.desc(n, h, w)
+        ep = L.EpilogueBf16(None, self.ps[self.name + "/bias"].data_ptr(), self.act, float(self.alpha), None, None)
+        with Timed(rt, tag):
+            L.check(rt.lib.vcg_conv_transpose2d_bf16_fwd(ctypes.byref(d), x.data_ptr(), wp.data_ptr(), y.data_ptr(), ctypes.byref(ep), rt.stream),
+                    "vcg_conv_transpose2d_bf16_fwd[%s]" % self.name)
+        return y, (x, y, d)
+
+
 class FinalConv9x9Bf16(Conv2D):
     """final/conv (model.py:290-291): Conv2D(3, 9) + tanh on a bf16 NHWC input with 256 channels, fp32 NCHW output.  Forward on
     vcg_conv9x9_to3_bf16_fwd; data gradient on vcg_conv9x9_to3_bf16_dgrad, which also applies the derivative of the LeakyReLU that
@@ -1357,29 +1264,19 @@ class FinalConv9x9Bf16(Conv2D):
         if cin != 256 or cout != 3 or k != 9:
             raise NotImplementedError("the bf16 final convolution is instantiated for 9x9, 256 -> 3 channels")
         super().__init__(name, cin, cout, k, 1, "same", act)
-        self._wf = self._wd = None
-        self._pvalid = False
+        self._pk = PackedOperand(self._pack, self)
 
-    def refresh(self):
-        super().refresh()
-        self._pvalid = False
-
-    def _packed(self):
-        rt = self.rt
-        if self._wf is None:
-            self._wf = torch.empty(L.FINAL9X9_WFRAG_BYTES, dtype=torch.uint8, device=rt.device)
-            self._wd = torch.empty(4 * L.FIRST9X9_WFRAG_BYTES, dtype=torch.uint8, device=rt.device)
-        if not self._pvalid:
-            w = self.ps[self.name + "/kernel"].data_ptr()
-            L.check(rt.lib.vcg_pack_final9x9_bf16(w, self._wf.data_ptr(), rt.stream), "vcg_pack_final9x9_bf16")
-            L.check(rt.lib.vcg_pack_conv9x9_3ch_bf16(w, 256, 1, self._wd.data_ptr(), rt.stream), "vcg_pack_conv9x9_3ch_bf16")
-            self._pvalid = True
-        return self._wf, self._wd
+    def _pack(self, out):
+        rt, w = self.rt, self.ps[self.name + "/kernel"]
+        wf, wd = out or (None, _bytes(rt, 4 * L.FIRST9X9_WFRAG_BYTES))
+        wf = pack_final9x9_bf16(rt, w, wf)
+        L.check(rt.lib.vcg_pack_conv9x9_3ch_bf16(w.data_ptr(), 256, 1, wd.data_ptr(), rt.stream), "vcg_pack_conv9x9_3ch_bf16")      # data gradient
+        return wf, wd
 
     def forward(self, x, residual=None, tag=None):
         rt = self.rt
         n, h, w, _ = x.shape
-        wf, _ = self._packed()
+        wf, _ = self._pk.get()
         d = self.desc(n, h, w)
         y = rt.empty(n, 3, h, w)
         with Timed(rt, tag):
@@ -1394,14 +1291,9 @@ class FinalConv9x9Bf16(Conv2D):
         rt = self.rt
         x, y, d = ctx
         n = d.n
-        db_done = False
-        if self.act != L.ACT_NONE:
-            dz = rt.empty(*dy.shape)
-            db = self.ps.grad(self.name + "/bias", which).data_ptr() if param_grads else None
-            ws, wsn = rt.workspace(rt.lib.vcg_act_bwd_workspace_bytes(n, 3, d.oh * d.ow))
-            L.check(rt.lib.vcg_act_bwd(y.data_ptr(), dy.data_ptr(), n, 3, d.oh * d.ow, self.act, 0.0, None, dz.data_ptr(), None, db, ws, wsn,
-                                       rt.stream), "vcg_act_bwd[%s]" % self.name)
-            dy, db_done = dz, True
+        db_done = self.act != L.ACT_NONE
+        if db_done:
+            dy = act_bwd_bias(self, y, dy, d, param_grads, which)
         if param_grads and d.w % 2 == 0:
             # bf16 weight gradient straight from the bf16 NHWC input (transposed LDS reads); dz enters as a bf16 MFMA operand
             ws, wsn = rt.workspace(max(rt.lib.vcg_conv9x9_to3_bf16_wgrad_workspace_bytes(ctypes.byref(d)),
@@ -1414,16 +1306,10 @@ class FinalConv9x9Bf16(Conv2D):
                                                rt.stream), "vcg_channel_sum[%s]" % self.name)
         elif param_grads:
             # odd widths: the fp32 kernel on an fp32 NCHW copy of the input (exact conversion)
-            x32 = from_bf16_nhwc(rt, x)
-            ws, wsn = rt.workspace(rt.lib.vcg_conv2d_wgrad_workspace_bytes(ctypes.byref(d)))
-            with Timed(rt, tag and tag + "_wgrad"):
-                L.check(rt.lib.vcg_conv2d_wgrad(ctypes.byref(d), x32.data_ptr(), dy.data_ptr(), self.ps.grad(self.name + "/kernel", which).data_ptr(),
-                                                None if db_done else self.ps.grad(self.name + "/bias", which).data_ptr(), ws, wsn, rt.stream),
-                        "vcg_conv2d_wgrad[%s]" % self.name)
-            del x32
+            self._wgrad_fp32(d, from_bf16_nhwc(rt, x), dy, which, not db_done, tag)
         if not need_dx:
             return None
-        _, wd = self._packed()
+        _, wd = self._pk.get()
         dx = torch.empty_like(x)
         if want_channel_sums:
             nrec = rt.lib.vcg_conv9x9_to3_bf16_dgrad_chsum_records(ctypes.byref(d))
@@ -1442,89 +1328,28 @@ class FinalConv9x9Bf16(Conv2D):
         return dx
 
 
-class NormActBf16(Layer):
+class NormActBf16(NormAct):
     """NormAct on bf16 NHWC (same parameters / names): statistics, affine and activation arithmetic in fp32."""
+    STATS, ACT_FWD, ACT_BWD = "vcg_norm_stats_bf16", "vcg_norm_act_fwd_bf16", "vcg_norm_act_bwd_bf16"
 
     def __init__(self, name, c, norm="batch", act=L.ACT_NONE, alpha=0.0, prelu_name=None):
-        super().__init__(name)
         if norm not in ("batch", "instance"):
             raise ValueError(norm)
-        self.c, self.norm, self.act, self.alpha, self.prelu_name = c, norm, act, alpha, prelu_name
+        super().__init__(name, c, norm, act, alpha, prelu_name)
 
-    declare = NormAct.declare
-    init_weights = NormAct.init_weights
-    _alpha_ptr = NormAct._alpha_ptr
-
-    def needs_stats(self, training):
-        """does forward(x, training) compute statistics of x (so that a producer's epilogue may hand them over)"""
-        return bool(training or self.norm == "instance")
-
-    def forward(self, x, training, residual=None, update_moving=True, stats=None):
-        """stats: (records, records per group) from the producing convolution's epilogue (Conv3x3Bf16 / Conv2DBf16.forward_stats) --
-        one vcg_norm_finalize_partials launch then replaces the statistics pass over x and vcg_norm_finalize"""
-        rt, ps, lib = self.rt, self.ps, self.rt.lib
+    def _dims(self, x):
         n, h, w, c = x.shape
-        hw = h * w
-        inst = self.norm == "instance"
-        rows = n if inst else 1
-        mode = L.NORM_INSTANCE if inst else L.NORM_BATCH
-        scale, shift, invstd = rt.empty(rows * c), rt.empty(rows * c), rt.empty(rows * c)
-        gamma = None if inst else ps[self.name + "/gamma"].data_ptr()
-        beta = None if inst else ps[self.name + "/beta"].data_ptr()
-        saved = None
-        if (training or inst) and stats is not None:
-            buf, nrec = stats
-            mean = rt.empty(rows * c)
-            mm = mv = None
-            if not inst and update_moving:
-                mm, mv = ps[self.name + "/moving_mean"].data_ptr(), ps[self.name + "/moving_variance"].data_ptr()
-            L.check(lib.vcg_norm_finalize_partials(buf.data_ptr(), nrec, rows, c, float(hw if inst else n * hw), gamma, beta,
-                                                   IN_EPS if inst else BN_EPS, mean.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                   invstd.data_ptr(), mm, mv, BN_MOMENTUM, 0 if inst else n * hw, rt.stream),
-                    "vcg_norm_finalize_partials[%s]" % self.name)
-            saved = (mean, invstd)
-        elif training or inst:
-            mean, var = rt.empty(rows * c), rt.empty(rows * c)
-            ws, wsn = rt.workspace(lib.vcg_norm_stats_bf16_workspace_bytes(n, c, hw, mode))
-            L.check(lib.vcg_norm_stats_bf16(x.data_ptr(), n, c, hw, mode, mean.data_ptr(), var.data_ptr(), ws, wsn, rt.stream),
-                    "vcg_norm_stats_bf16[%s]" % self.name)
-            mm = mv = None
-            if not inst and update_moving:
-                mm, mv = ps[self.name + "/moving_mean"].data_ptr(), ps[self.name + "/moving_variance"].data_ptr()
-            L.check(lib.vcg_norm_finalize(mean.data_ptr(), var.data_ptr(), gamma, beta, c, rows, IN_EPS if inst else BN_EPS, scale.data_ptr(),
-                                          shift.data_ptr(), invstd.data_ptr(), mm, mv, BN_MOMENTUM, 0 if inst else n * hw, rt.stream),
-                    "vcg_norm_finalize")
-            saved = (mean, invstd)
-        else:
-            L.check(lib.vcg_norm_finalize(ps[self.name + "/moving_mean"].data_ptr(), ps[self.name + "/moving_variance"].data_ptr(), gamma, beta, c, 1,
-                                          BN_EPS, scale.data_ptr(), shift.data_ptr(), invstd.data_ptr(), None, None, 0.0, 0, rt.stream),
-                    "vcg_norm_finalize")
-        y = torch.empty_like(x)
-        L.check(lib.vcg_norm_act_fwd_bf16(x.data_ptr(), n, c, hw, scale.data_ptr(), shift.data_ptr(), 1 if inst else 0, self.act, float(self.alpha),
-                                          self._alpha_ptr(), _ptr(residual), y.data_ptr(), rt.stream), "vcg_norm_act_fwd_bf16[%s]" % self.name)
-        return y, (x, saved, mode, (n, c, hw))
+        return n, c, h * w
 
-    def backward(self, ctx, dy, param_grads=True, which=0):
-        rt, ps, lib = self.rt, self.ps, self.rt.lib
-        x, saved, mode, (n, c, hw) = ctx
-        if saved is None:
-            raise RuntimeError("backward through inference-mode normalisation is not defined")
-        mean, invstd = saved
-        inst = self.norm == "instance"
-        gamma = None if inst else ps[self.name + "/gamma"].data_ptr()
-        beta = None if inst else ps[self.name + "/beta"].data_ptr()
-        dgamma = dbeta = dalpha = None
-        if param_grads:
-            if not inst:
-                dgamma, dbeta = ps.grad(self.name + "/gamma", which).data_ptr(), ps.grad(self.name + "/beta", which).data_ptr()
-            if self.act == L.ACT_PRELU:
-                dalpha = ps.grad(self.prelu_name + "/alpha", which).data_ptr()
-        dx = torch.empty_like(x)
-        ws, wsn = rt.workspace(lib.vcg_norm_act_bwd_bf16_workspace_bytes(n, c, hw, mode))
-        L.check(lib.vcg_norm_act_bwd_bf16(x.data_ptr(), dy.data_ptr(), n, c, hw, mode, mean.data_ptr(), invstd.data_ptr(), gamma, beta, self.act,
-                                          float(self.alpha), self._alpha_ptr(), 1, dx.data_ptr(), dgamma, dbeta, dalpha, ws, wsn, rt.stream),
-                "vcg_norm_act_bwd_bf16[%s]" % self.name)
-        return dx
+    def _like(self, x):
+        return torch.empty_like(x)
+
+    def _finalize_partials(self, stats, rows, c, count, gamma, beta, eps, mean, scale, shift, invstd, mm, mv, unbiased_n):
+        """(records, records per group) of Conv3x3Bf16 / Conv5x5Bf16 / Conv2DBf16.forward_stats"""
+        buf, nrec = stats
+        L.check(self.rt.lib.vcg_norm_finalize_partials(buf.data_ptr(), nrec, rows, c, count, gamma, beta, eps, mean.data_ptr(), scale.data_ptr(),
+                                                       shift.data_ptr(), invstd.data_ptr(), mm, mv, BN_MOMENTUM, unbiased_n, self.rt.stream),
+                "vcg_norm_finalize_partials[%s]" % self.name)
 
 
 # =================================================================================================

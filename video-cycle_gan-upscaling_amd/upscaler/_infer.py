@@ -31,8 +31,6 @@ import torch
 from . import _engine as E
 from . import _lib as L
 
-BN_EPS = 1e-3          # keras.layers.BatchNormalization default
-
 
 class Bf16Generator:
     TAIL_CHANNELS = 256        # channels of the up-sampling stages' outputs (model.py:288): what the 4 GiB rule of _tail_chunk counts
@@ -63,15 +61,10 @@ class Bf16Generator:
         """3x3 layers of the k3 topology: [tap][out][in] bf16 (Conv2D (k,k,in,out) with transpose=1, Conv2DTranspose (k,k,out,in) with
         transpose=0); every other layer: the generic kernels' MFMA fragments (vcg_pack_conv_frag_bf16: mode 0 for a Conv2D, mode 1 for a
         Conv2DTranspose, whose kernel is the data gradient's of a stride-2 Conv2D)"""
-        rt, taps = self.rt, conv.k * conv.k
-        out = torch.empty(taps, conv.cout, conv.cin, dtype=torch.bfloat16, device=rt.device)
+        w, taps = conv.ps[conv.name + "/kernel"], conv.k * conv.k
         if self._generic(conv, transpose):
-            L.check(rt.lib.vcg_pack_conv_frag_bf16(conv.ps[conv.name + "/kernel"].data_ptr(), taps, conv.cout, conv.cin, 1 - transpose,
-                                                   out.data_ptr(), rt.stream), "vcg_pack_conv_frag_bf16")
-            return out
-        L.check(rt.lib.vcg_pack_conv_kernel_bf16(conv.ps[conv.name + "/kernel"].data_ptr(), taps, conv.cout, conv.cin, transpose, 0,
-                                                 out.data_ptr(), rt.stream), "vcg_pack_conv_kernel_bf16")
-        return out
+            return E.pack_conv_frag_bf16(self.rt, w, taps, conv.cout, conv.cin, 1 - transpose)
+        return E.pack_conv_kernel_bf16(self.rt, w, taps, conv.cout, conv.cin, transpose, 0)
 
     @staticmethod
     def _generic(conv, transpose):
@@ -89,7 +82,7 @@ class Bf16Generator:
         E.axpby(rt, ps[conv.name + "/bias"], mean, -1.0, 1.0)
         scale, shift = rt.empty(c), rt.empty(c)
         L.check(rt.lib.vcg_norm_finalize(mean.data_ptr(), ps[norm.name + "/moving_variance"].data_ptr(), ps[norm.name + "/gamma"].data_ptr(),
-                                         ps[norm.name + "/beta"].data_ptr(), c, 1, BN_EPS, scale.data_ptr(), shift.data_ptr(), None, None, None,
+                                         ps[norm.name + "/beta"].data_ptr(), c, 1, E.BN_EPS, scale.data_ptr(), shift.data_ptr(), None, None, None,
                                          0.0, 0, rt.stream), "vcg_norm_finalize")
         return scale, shift
 
@@ -106,14 +99,9 @@ class Bf16Generator:
         # one weight set per up-sampling stage: 64 -> 256, then 256 -> 256 (model.py:286-288)
         self.ups = [(self._pack(up, 0), up.ps[up.name + "/bias"], float(up.alpha), up.cin) for up in m.ups]
         self.up = self.ups[0][:3]
-        wf = torch.empty(L.FINAL9X9_WFRAG_BYTES, dtype=torch.uint8, device=rt.device)
-        L.check(rt.lib.vcg_pack_final9x9_bf16(m.c_fin.ps[m.c_fin.name + "/kernel"].data_ptr(), wf.data_ptr(), rt.stream),
-                "vcg_pack_final9x9_bf16")
-        self.final = (wf, m.c_fin.ps[m.c_fin.name + "/bias"])
-        w0 = torch.empty(L.FIRST9X9_WFRAG_BYTES, dtype=torch.uint8, device=rt.device)
-        L.check(rt.lib.vcg_pack_first9x9_bf16(m.c_init.ps[m.c_init.name + "/kernel"].data_ptr(), w0.data_ptr(), rt.stream),
-                "vcg_pack_first9x9_bf16")
-        self.first = (w0, m.c_init.ps[m.c_init.name + "/bias"], m.c_init.ps[m.a_init.prelu_name + "/alpha"])
+        self.final = (E.pack_final9x9_bf16(rt, m.c_fin.ps[m.c_fin.name + "/kernel"]), m.c_fin.ps[m.c_fin.name + "/bias"])
+        self.first = (E.pack_first9x9_bf16(rt, m.c_init.ps[m.c_init.name + "/kernel"]), m.c_init.ps[m.c_init.name + "/bias"],
+                      m.c_init.ps[m.a_init.prelu_name + "/alpha"])
         self._graphs.clear()          # recorded graphs hold the old parameter buffers
 
     # ---- one forward pass (22 launches) -----------------------------------------------------------------------
@@ -296,13 +284,9 @@ class Bf16AttentionGenerator(Bf16Generator):
         return not transpose or conv.k != 3
 
     def _pack_gate(self, conv):
-        rt = self.rt
-        nbytes = rt.lib.vcg_conv_in_gate_bf16_wfrag_bytes(conv.cin, conv.k, conv.k, conv.cout)
-        if nbytes == 0:
+        out = E.pack_conv_in_gate_bf16(self.rt, conv.ps[conv.name + "/kernel"], conv.cin, conv.k, conv.k, conv.cout)
+        if out is None:
             raise NotImplementedError(self.SERVED)
-        out = torch.empty(nbytes, dtype=torch.uint8, device=rt.device)
-        L.check(rt.lib.vcg_pack_conv_in_gate_bf16(conv.ps[conv.name + "/kernel"].data_ptr(), conv.cin, conv.k, conv.k, conv.cout, out.data_ptr(),
-                                                  rt.stream), "vcg_pack_conv_in_gate_bf16")
         return out, conv.ps[conv.name + "/bias"]
 
     def refresh(self):
@@ -327,13 +311,9 @@ class Bf16AttentionGenerator(Bf16Generator):
             self.ups.append((self._pack_gate(ly[n + "/attention"]), self._pack(up, 0), ps[up.name + "/bias"], float(up.alpha), up.cin, up.cout,
                              ps[ta.name + "/kernel"], ps[ta.name + "/bias"]))
         cf = ly["final/conv"]
-        wf = torch.empty(rt.lib.vcg_conv9x9_to3_bf16_wfrag_bytes(cf.cin), dtype=torch.uint8, device=rt.device)
-        L.check(rt.lib.vcg_pack_conv9x9_to3_bf16(ps[cf.name + "/kernel"].data_ptr(), cf.cin, wf.data_ptr(), rt.stream), "vcg_pack_conv9x9_to3_bf16")
-        self.final = (wf, ps[cf.name + "/bias"], cf.cin)
+        self.final = (E.pack_conv9x9_to3_bf16(rt, ps[cf.name + "/kernel"], cf.cin), ps[cf.name + "/bias"], cf.cin)
         c0 = ly["initial/conv"]
-        w0 = torch.empty(L.FIRST9X9_WFRAG_BYTES, dtype=torch.uint8, device=rt.device)
-        L.check(rt.lib.vcg_pack_first9x9_bf16(ps[c0.name + "/kernel"].data_ptr(), w0.data_ptr(), rt.stream), "vcg_pack_first9x9_bf16")
-        self.first = (w0, ps[c0.name + "/bias"], ps["initial/prelu/alpha"])
+        self.first = (E.pack_first9x9_bf16(rt, ps[c0.name + "/kernel"]), ps[c0.name + "/bias"], ps["initial/prelu/alpha"])
         self._graphs.clear()          # recorded graphs hold the old parameter buffers
 
     def _buffers(self, n, h, w):
