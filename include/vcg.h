@@ -337,6 +337,20 @@ int vcg_conv9x9_to3_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* 
  * (vcg_conv9x9_to3_bf16_dgrad*) stay 256-only. */
 size_t vcg_conv9x9_to3_bf16_wfrag_bytes(int32_t cin);
 int vcg_pack_conv9x9_to3_bf16(const void* w, int32_t cin, void* out, hipStream_t stream);
+/* final/conv over a window of rows: what lets an inference engine run the tail on row bands of a frame and write uint8 frames directly.
+ * d describes the INPUT band x: bf16 NHWC [n][d->h][d->w][cin], cin 128 or 256; rows outside [0, d->h) are zero padding, as in the
+ * whole-image entry point above.  Only output rows [row0, row0+rows) of the band are computed.  They are stored as rows
+ * [y_row0, y_row0+rows) of images of y_h rows and d->w columns:
+ *   out_kind VCG_OUT_F32_NCHW: y = float [n][3][y_h][w], bit for bit the values the whole-image entry point stores for those rows
+ *   out_kind VCG_OUT_U8_NHWC:  y = uint8 [n][y_h][w][3], value = clamp(rintf((v + 1.f) * 127.5f), 0, 255), v the fp32 value the F32 form
+ *                              stores (upscaling/upscaler/data.py:253-256; the expression of the fp32 NCHW -> uint8 frame conversion above)
+ * Nothing outside those rows of y is written.  No workspace.  VCG_E_SHAPE: rows <= 0, row0 < 0, row0+rows > d->h, y_row0 < 0,
+ * y_row0+rows > y_h; VCG_E_UNSUPPORTED: an unknown out_kind, whatever the whole-image entry point refuses, and a band whose
+ * (d->h + 8) * d->w * cin * 2 bytes (+ 64 KiB) do not fit 32-bit offsets -- band the image further. */
+#define VCG_OUT_F32_NCHW 0
+#define VCG_OUT_U8_NHWC 1
+int vcg_conv9x9_to3_bf16_fwd_window(const vcg_conv_desc* d, const void* x, const void* wfrag, const void* bias, int32_t tanh_act,
+                                    int32_t out_kind, void* y, int32_t row0, int32_t rows, int32_t y_row0, int32_t y_h, hipStream_t stream);
 
 /* initial/conv of the generator (upscaling/upscaler/model.py:275-276): Conv2D(64, 9, 'same') + bias + PReLU from the
  * fp32 NCHW frames to bf16 NHWC -- the entry into the bf16 layout.  wfrag: VCG_FIRST9X9_WFRAG_BYTES bytes of MFMA operand

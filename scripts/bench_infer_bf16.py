@@ -13,8 +13,16 @@ batch.  Prints one JSON line per run, shaped like ``bench.py --config c5``'s.
            vcg_conv2d_bf16_fwd (folded BN + PReLU epilogue) against vcg_conv2d_nhwc_bf16_fwd (bias only) -- the same generic kernels, so the
            pair prices the epilogue
 
+  --u8     host-to-host frames/s of ``predict`` (fp32 numpy in and out) against the uint8 path with synchronous copies (a loop of this
+           script's) and against ``upscale_frames`` (the copies overlapped), --u8-batches batches per call, --ab-reps alternated
+           repetitions, median and min-max; then (orig generator) one launch of final/conv on the engine's last up-sampling tensor, fp32
+           NCHW against uint8 NHWC output, by HIP events
+  --band-rows R   run the tail in bands of R low-res rows (default: the automatic plan); the result line says how many bands
+  --band-sweep R [R ...]   device time of one replayed batch by HIP events, unbanded and in bands of each R low-res rows, each banded
+           output compared with the unbanded one
+
 Usage: python scripts/bench_infer_bf16.py [--lr-size 128] [--lr-width W] [--batch 32] [--kernel-size 5] [--upscale 4] [--res-blocks 16]
-                                          [--steps 10] [--warmup 3] [--fp32] [--full]"""
+                                          [--steps 10] [--warmup 3] [--fp32] [--full] [--u8] [--band-rows R] [--band-sweep R [R ...]]"""
 import argparse
 import ctypes
 import json
@@ -89,6 +97,10 @@ def main():
     ap.add_argument("--full", action="store_true")
     ap.add_argument("--ab-reps", type=int, default=5)
     ap.add_argument("--generator", choices=("orig", "attention"), default="orig")
+    ap.add_argument("--u8", action="store_true")
+    ap.add_argument("--u8-batches", type=int, default=4)
+    ap.add_argument("--band-rows", type=int, default=None)
+    ap.add_argument("--band-sweep", type=int, nargs="+", default=None, metavar="R")
     args = ap.parse_args()
 
     import torch
@@ -106,13 +118,14 @@ def main():
     rt = inf.rt
     g1 = torch.Generator().manual_seed(1234)
     x = PD.frames_u8_to_device(torch.randint(0, 256, (B, h, w, 3), generator=g1, dtype=torch.uint8))
-    inf.capture(B, h, w)
+    br = args.band_rows
+    inf.capture(B, h, w, L.OUT_F32_NCHW, br)
     for _ in range(args.warmup):
-        inf.replay(x)
+        inf.replay(x, br)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        inf.replay(x)
+        inf.replay(x, br)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     fl = flop_frame_attention(h, w, k, f, res) if att else flop_frame(h, w, k, f, res)
@@ -123,8 +136,15 @@ def main():
           "peak_share": round(fl * B * args.steps / dt / PEAK_BF16, 3),
           "config": {"workload": "%s((%d,%d,3),k=%d,x%d,res=%d).to_inference_bf16(), BN folded, bf16 NHWC activations, "
                                  "fp32 accumulate, batch %d, one hipGraph replay per batch" % (make.__name__, f * h, f * w, k, f, res, B),
-                     "global_batch": B, "frame": frame, "launch": "hipGraph replay"}}
+                     "global_batch": B, "frame": frame, "launch": "hipGraph replay", "band_rows": br,
+                     "tail_bands": len(inf._plan(B, h, w, br)[1]), "tail_frames_per_launch": inf._plan(B, h, w, br)[0]}}
     print(json.dumps(bf), flush=True)
+
+    if args.u8:
+        u8_host_to_host(args, inf, h, w, f, B, frame)
+
+    if args.band_sweep:
+        band_sweep(args, inf, x, h, w, k, f, B)
 
     if args.fp32:
         b32 = min(args.fp32_batch, B)
@@ -148,6 +168,98 @@ def main():
 
     if args.full:
         (full_attention if att else full)(args, inf, x, h, w, k, f, res, B)
+
+
+def band_sweep(args, inf, x, h, w, k, f, B):
+    """device time of one replayed batch by HIP events, unbanded and in bands of each height given, and whether the banded fp32 output
+    equals the unbanded one bit for bit (where it does not -- a band below the generic transposed convolution's kernel threshold, DESIGN.md
+    section 9.5 -- the largest difference)"""
+    import statistics
+
+    import torch
+    ref = inf.replay(x, None).clone()
+    for br in [None] + list(args.band_sweep):
+        y = inf.replay(x, br)
+        torch.cuda.synchronize()
+        diff = float((y - ref).abs().max())
+        ms = [time_events(lambda: inf.replay(x, br), 5) for _ in range(max(5, args.ab_reps))]
+        ch, bands = inf._plan(B, h, w, br)
+        print(json.dumps({"kind": "band_sweep", "k": k, "f": f, "lr": "%dx%d" % (h, w), "batch": B, "band_rows": br, "bands": len(bands),
+                          "frames_per_launch": ch, "identical_to_unbanded": bool(torch.equal(y, ref)), "max_abs_diff": diff,
+                          "ms_per_batch_median": round(statistics.median(ms), 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3)}),
+              flush=True)
+
+
+def u8_host_to_host(args, inf, h, w, f, B, frame):
+    """frames/s from host memory to host memory: predict (fp32 NHWC numpy in and out) against upscale_frames (uint8 in and out), the arms
+    alternated; then final/conv alone with its two output forms"""
+    import statistics
+
+    import numpy as np
+    import torch
+    from upscaler import _lib as L
+    rt, lib, br = inf.rt, inf.rt.lib, args.band_rows
+    N = B * args.u8_batches
+    u8 = np.random.RandomState(5).randint(0, 256, (N, h, w, 3)).astype(np.uint8)
+    xf = (u8 / 127.5 - 1).astype(np.float32)
+    def synchronous():
+        """the uint8 path with its copies on the compute stream, one after the other: the form upscale_frames' overlapped copies are
+        measured against (the same graphs, the same conversion kernel)"""
+        t = torch.from_numpy(u8)
+        out = np.empty((N, f * h, f * w, 3), dtype=np.uint8)
+        for i in range(0, N, B):
+            xb = t[i:i + B].to(rt.device)
+            nb = xb.shape[0]
+            g, xin, y = inf.capture(nb, h, w, L.OUT_U8_NHWC, br)
+            L.check(lib.vcg_frames_u8_to_nchw(xb.data_ptr(), xin.data_ptr(), nb, h, w, 3, rt.stream), "vcg_frames_u8_to_nchw")
+            g.replay()
+            torch.from_numpy(out[i:i + nb]).copy_(y)
+        return out
+
+    arms = {"predict (fp32 in/out)": lambda: inf.predict(xf, batch_size=B, band_rows=br),
+            "uint8 in/out, synchronous copies (this script's loop)": synchronous,
+            "upscale_frames (uint8 in/out, overlapped copies)": lambda: inf.upscale_frames(u8, batch_size=B, band_rows=br)}
+    ref = None
+    for name, fn in arms.items():                    # warm-up: graphs recorded, staging buffers pinned; the uint8 arms agree
+        got = fn()
+        if got.dtype == np.uint8:
+            assert ref is None or np.array_equal(ref, got), name
+            ref = got
+    fps = {name: [] for name in arms}
+    for _ in range(max(5, args.ab_reps)):
+        for name, fn in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            fps[name].append(N / (time.perf_counter() - t0))
+    for name, v in fps.items():
+        print(json.dumps({"kind": "host_to_host", "arm": name, "frame": frame, "batch": B, "frames_per_call": N, "reps": len(v),
+                          "frames_per_s_median": round(statistics.median(v), 1), "frames_per_s_min": round(min(v), 1),
+                          "frames_per_s_max": round(max(v), 1)}), flush=True)
+    if args.generator != "orig":          # the launch comparison below reads Bf16Generator's buffers (256 channels)
+        return
+    # one launch of final/conv on the last up-sampling stage's tensor (whatever the last pass left in it)
+    Bf = inf._buffers(B, h, w)
+    src = Bf["us"][-1]
+    ch, hh, ww = src.shape[0], src.shape[1], src.shape[2]
+    wf, bf_ = inf.final
+    df = L.ConvDesc(ch, 256, hh, ww, 3, hh, ww, 9, 9, 1, 4, 4)
+    y32 = torch.empty(ch, 3, hh, ww, device=rt.device)
+    y8 = torch.empty(ch, hh, ww, 3, dtype=torch.uint8, device=rt.device)
+    st = rt.stream
+    forms = {"vcg_conv9x9_to3_bf16_fwd (fp32 NCHW)": lambda: L.check(lib.vcg_conv9x9_to3_bf16_fwd(
+                 ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, y32.data_ptr(), st), "final"),
+             "window, fp32 NCHW": lambda: L.check(lib.vcg_conv9x9_to3_bf16_fwd_window(
+                 ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, L.OUT_F32_NCHW, y32.data_ptr(), 0, hh, 0, hh, st), "final"),
+             "window, uint8 NHWC": lambda: L.check(lib.vcg_conv9x9_to3_bf16_fwd_window(
+                 ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, L.OUT_U8_NHWC, y8.data_ptr(), 0, hh, 0, hh, st), "final")}
+    ms = {name: [] for name in forms}
+    for _ in range(max(5, args.ab_reps)):
+        for name, fn in forms.items():
+            ms[name].append(time_events(fn, 5))
+    for name, v in ms.items():
+        print(json.dumps({"kind": "final_conv_launch", "form": name, "shape": "%d x %dx%d x 256" % (ch, hh, ww), "reps": len(v),
+                          "ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4)}), flush=True)
 
 
 def full(args, inf, x, h, w, k, f, res, B):

@@ -11,7 +11,8 @@ share of each segment:
     v2  conv3x3_c64_bf16_v2_kernel, the trunk at C5's shape                                   [batch] [plain|prelu|add] [launches]
     i9  conv_c3to64_bf16_kernel<9,3,1> as final/conv's data gradient (3 -> 256, LeakyReLU mask)    [batch] [h] [w] [mask 0/1]
     ct  convt3x3_c64_bf16_kernel, the up-sampling block's transposed convolution (64 -> 256)       [batch] [h] [w]
-    f9  conv9x9_c256to3_bf16_kernel, final/conv                                                    [batch] [h] [w] [launches]
+    f9  conv9x9_c256to3_bf16_kernel, final/conv                                                    [batch] [h] [w] [launches] [full|f32|u8]
+        (full: vcg_conv9x9_to3_bf16_fwd; f32 / u8: the whole image as one window of vcg_conv9x9_to3_bf16_fwd_window, fp32 NCHW / uint8 NHWC out)
     wg  wgrad3x3_c64_bf16_kernel, the trunk's weight gradient                                      [batch] [h] [w]
 `run` takes one variant: an A/B table (e.g. ct with and without --variant CT_NO_DEFER) is two invocations side by side.
 The stamps are those of the LAST launch: many launches = the sustained state.  Read the shares, not the run time, of such a build.
@@ -143,7 +144,7 @@ def run_ct(lib, L, torch, args):
 
 
 def run_f9(lib, L, torch, args):
-    B, h, w, iters = arg(args, 0, 8), arg(args, 1, 512), arg(args, 2, 512), arg(args, 3, 20)
+    B, h, w, iters, out = arg(args, 0, 8), arg(args, 1, 512), arg(args, 2, 512), arg(args, 3, 20), arg(args, 4, "full", str)
     dev = torch.device("cuda:0")
     x = torch.randn(B, h, w, 256, device=dev).to(torch.bfloat16)
     wk = torch.randn(9, 9, 256, 3, device=dev) * 0.01
@@ -153,8 +154,15 @@ def run_f9(lib, L, torch, args):
     st = torch.cuda.current_stream().cuda_stream
     assert lib.vcg_pack_final9x9_bf16(wk.data_ptr(), wf.data_ptr(), st) == 0
     d = L.ConvDesc(B, 256, h, w, 3, h, w, 9, 9, 1, 4, 4)
-    us = timed(lambda: lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), bias.data_ptr(), 1, y.data_ptr(), st), iters)
-    print("batch %d %dx%d: %.1f us per launch (events, %d launches)" % (B, h, w, us, iters))
+    if out == "full":
+        go = lambda: lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), bias.data_ptr(), 1, y.data_ptr(), st)
+    else:
+        kind = {"f32": L.OUT_F32_NCHW, "u8": L.OUT_U8_NHWC}[out]
+        y8 = torch.empty(B, h, w, 3, dtype=torch.uint8, device=dev)
+        go = lambda: lib.vcg_conv9x9_to3_bf16_fwd_window(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), bias.data_ptr(), 1, kind,
+                                                         (y8 if out == "u8" else y).data_ptr(), 0, h, 0, h, st)
+    us = timed(go, iters)
+    print("batch %d %dx%d, output %s: %.1f us per launch (events, %d launches)" % (B, h, w, out, us, iters))
     full = sums(lib.vcg_debug_f9_stamps, 512, 4, 8)
     full = full[full[:, 0, 5] > 0]
     rows = full[:, :, 5]

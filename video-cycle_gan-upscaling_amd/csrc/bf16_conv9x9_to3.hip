@@ -34,6 +34,19 @@ struct F9Params {
     int n, h, w_, strips, segs, sh, total;      // sh: output rows per work item (8 halo rows are recomputed per item)
     int tanh_act;
 };
+// the window forms (OUT != F9_FULL): output rows [row0, row0 + rows) of x's images are computed and stored as rows [y_row0, y_row0 + rows)
+// of images of y_h rows.  The new fields follow F9Params': the whole-image kernels keep their kernarg block, offsets and size
+struct F9WinParams : F9Params {
+    int row0, rows, y_row0, y_h;
+};
+// what a launch stores: the whole image as fp32 NCHW (vcg_conv9x9_to3_bf16_fwd), or a window of rows as fp32 NCHW / uint8 NHWC frames
+// (vcg_conv9x9_to3_bf16_fwd_window)
+constexpr int F9_FULL = 0, F9_WIN_F32 = 1, F9_WIN_U8 = 2;
+
+// data.py:253-256, the expression of nchw_to_u8_kernel (elementwise.hip): uint8(around((a + 1) * 127.5)), round-half-even, clamped
+__device__ __forceinline__ unsigned char f9_to_u8(float v) {
+    return (unsigned char)fminf(fmaxf(rintf((v + 1.f) * 127.5f), 0.f), 255.f);
+}
 
 // Diagnostic build only (-DVCG_STAMPS, scripts/micro/stamps.py): s_memtime brackets around the five segments of an input row, summed
 // per wave and written to a buffer of their own; no stamp executes in the shipped library.
@@ -49,6 +62,14 @@ __device__ __forceinline__ float fast_tanh(float x) {
     return copysignf(a < 0.015625f ? small : t, x);
 }
 
+// window forms: output row yo of the input image is row y_row0 + (yo - row0) of an image of y_h rows
+template <int OUT>
+__device__ __forceinline__ void f9_store_win(const F9WinParams& p, int img, int yo, int x, int co, float v) {
+    const int yr = p.y_row0 + (yo - p.row0);
+    if constexpr (OUT == F9_WIN_U8) ((unsigned char*)p.y)[((long)(img * p.y_h + yr) * p.w_ + x) * 3 + co] = f9_to_u8(v);
+    else p.y[((long)(img * 3 + co) * p.y_h + yr) * p.w_ + x] = v;
+}
+
 // BUF: the row slices are fetched through the image's buffer descriptor (pixels outside the image read as zero by the range check) with two
 // lane constants; the pointer form (BUF = false: images too large for a descriptor) keeps nine 64-bit lane addresses, which at this kernel's
 // 256-register budget are SPILLED -- hipcc then waits vmcnt(0) in front of every reload, i.e. for every earlier piece of the row: the nine
@@ -57,8 +78,14 @@ __device__ __forceinline__ float fast_tanh(float x) {
 // 128-channel one of make_upscaler_attention (model.py:326).  A wave keeps its 64 channels, its 144 weight registers and its row slice
 // either way; a pixel is NW x 128 bytes, the workgroup NW x 64 threads and NW x 18 KiB of row buffers (so twice as many fit a CU), and
 // the NW partial rows meet in LDS as before.
-template <bool BUF, int NW = 4>
-__global__ __launch_bounds__(64 * NW, 2) void conv9x9_c256to3_bf16_kernel(F9Params p) {
+// OUT: F9_FULL keeps the whole-image form's code exactly.  The window forms segment [row0, row0 + rows) instead of [0, h) -- the DMA of
+// rows y0-4 .. y1+4 is the same, a row outside [0, h) still reads as zero -- and place the rows in an image of y_h rows.  F9_WIN_U8: the
+// row's 64 pixels are 192 consecutive bytes of the NHWC frame; thread t of the 192 finishes BYTE t (co = t % 3, col = t / 3, the
+// same four-term sum in the same order), so each of the three waves issues one byte store per lane to 64 consecutive addresses.  A row's
+// base (row * w + x0) * 3 is not dword-aligned for general w: byte stores need no alignment case.
+// P: the kernarg struct, F9Params for F9_FULL (its kernarg block is the one it always had) and F9WinParams for the window forms.
+template <bool BUF, int NW = 4, int OUT = F9_FULL, class P = F9Params>
+__global__ __launch_bounds__(64 * NW, 2) void conv9x9_c256to3_bf16_kernel(P p) {
     constexpr int PB = NW * 128;                                      // bytes per pixel
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long f0 = 0, f1 = 0, f2 = 0, f3 = 0, f4 = 0, f5 = 0, f6 = 0, fs_shift = 0, fs_wait = 0, fs_dma = 0, fs_mfma = 0, fs_bar = 0, fs_out = 0, f_rows = 0;
@@ -92,7 +119,8 @@ __global__ __launch_bounds__(64 * NW, 2) void conv9x9_c256to3_bf16_kernel(F9Para
     // (recomputed per row from three lane constants: 18 more live VGPRs would spill)
     const int l3 = lane >> 3, l4 = lane >> 4, l7 = lane & 7;
     float bias = 0.f, bias3[3] = {0.f, 0.f, 0.f};
-    if constexpr (NW == 4) bias = (p.bias && tid < 192) ? p.bias[tid >> 6] : 0.f;
+    if constexpr (NW == 4 && OUT == F9_WIN_U8) bias = (p.bias && tid < 192) ? p.bias[tid % 3] : 0.f;
+    else if constexpr (NW == 4) bias = (p.bias && tid < 192) ? p.bias[tid >> 6] : 0.f;
     else if (p.bias) bias3[0] = p.bias[0], bias3[1] = p.bias[1], bias3[2] = p.bias[2];
     (void)bias, (void)bias3;
     const unsigned char* zeros = (const unsigned char*)(p.wfrag + NW * (F_NFRAG / 4));      // padding pixels are fetched from here
@@ -104,7 +132,8 @@ __global__ __launch_bounds__(64 * NW, 2) void conv9x9_c256to3_bf16_kernel(F9Para
 
     for (int item = blockIdx.x; item < p.total; item += gridDim.x) {
         const int seg = item % p.segs, i2 = item / p.segs, strip = i2 % p.strips, img = i2 / p.strips;
-        const int x0 = strip * 64, y0 = seg * p.sh, y1 = min(y0 + p.sh, p.h);
+        const int x0 = strip * 64, y0 = [&] { if constexpr (OUT == F9_FULL) return seg * p.sh; else return p.row0 + seg * p.sh; }(),
+                  y1 = min(y0 + p.sh, [&] { if constexpr (OUT == F9_FULL) return p.h; else return p.row0 + p.rows; }());
         const vcg_rsrc rs = make_rsrc(p.x + img * img_bytes, (unsigned long)img_bytes);
 
         auto dma = [&](int yi, int buf) {
@@ -216,23 +245,31 @@ __global__ __launch_bounds__(64 * NW, 2) void conv9x9_c256to3_bf16_kernel(F9Para
             VCG_STAMP(f4);
             if constexpr (NW == 4) {
                 if (yo >= y0 && tid < 192) {
-                    const int co = tid >> 6, col = tid & 63;
+                    int co_, col_;                                   // F9_WIN_U8: thread t finishes byte t of the row
+                    if constexpr (OUT == F9_WIN_U8) { co_ = tid % 3; col_ = tid / 3; } else { co_ = tid >> 6; col_ = tid & 63; }
+                    const int co = co_, col = col_;
                     const float* q = part + slot * 4 * 3 * 64 + co * 64 + col;
                     float v = ((q[0] + q[3 * 64]) + (q[2 * 3 * 64] + q[3 * 3 * 64])) + bias;
                     if (p.tanh_act) v = fast_tanh(v);
-                    if (x0 + col < p.w_) p.y[((long)(img * 3 + co) * p.h + yo) * p.w_ + x0 + col] = v;
+                    if constexpr (OUT == F9_FULL) {
+                        if (x0 + col < p.w_) p.y[((long)(img * 3 + co) * p.h + yo) * p.w_ + x0 + col] = v;
+                    } else if (x0 + col < p.w_) f9_store_win<OUT>(p, img, yo, x0 + col, co, v);
                 }
             } else if (yo >= y0) {
                 // 3 x 64 outputs of the row on NW x 64 threads
                 for (int o = tid; o < 192; o += 64 * NW) {
-                    const int co = o >> 6, col = o & 63;
+                    int co_, col_;
+                    if constexpr (OUT == F9_WIN_U8) { co_ = o % 3; col_ = o / 3; } else { co_ = o >> 6; col_ = o & 63; }
+                    const int co = co_, col = col_;
                     const float* q = part + slot * NW * 3 * 64 + co * 64 + col;
                     float v = q[0];
 #pragma unroll
                     for (int k = 1; k < NW; ++k) v += q[k * 3 * 64];
                     v += co == 0 ? bias3[0] : co == 1 ? bias3[1] : bias3[2];
                     if (p.tanh_act) v = fast_tanh(v);
-                    if (x0 + col < p.w_) p.y[((long)(img * 3 + co) * p.h + yo) * p.w_ + x0 + col] = v;
+                    if constexpr (OUT == F9_FULL) {
+                        if (x0 + col < p.w_) p.y[((long)(img * 3 + co) * p.h + yo) * p.w_ + x0 + col] = v;
+                    } else if (x0 + col < p.w_) f9_store_win<OUT>(p, img, yo, x0 + col, co, v);
                 }
             }
             VCG_STAMP(f5);
@@ -273,6 +310,69 @@ __global__ void pack_final9x9_kernel(const float* __restrict__ w, uint4* __restr
     out[idx] = __builtin_bit_cast(uint4, v);
 }
 
+int f9_check_desc(const vcg_conv_desc* d) {
+    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->oh != d->h || d->ow != d->w) return VCG_E_SHAPE;
+    if ((d->cin != 256 && d->cin != 128) || d->cout != 3 || d->kh != 9 || d->kw != 9 || d->stride != 1 || d->pad_top != 4 || d->pad_left != 4) return VCG_E_UNSUPPORTED;
+    return VCG_OK;
+}
+
+// plan and launch of both entry points.  out = F9_FULL: the whole image (row0 = 0, rows = d->h); the window forms compute output rows
+// [row0, row0 + rows) only and exist for the descriptor form alone
+int f9_launch(const vcg_conv_desc* d, const void* x, const void* wfrag, const void* bias, int tanh_act, void* y, int out, int row0, int rows,
+              int y_row0, int y_h, hipStream_t stream) {
+    const int nw = d->cin / 64;
+    const int max_grid = F9_MAX_GRID * 4 / nw;                    // half the threads and LDS per workgroup: twice the workgroups per CU
+    // the descriptor form needs the image, four rows above and four below it inside 32-bit offsets
+    const bool buf = ((long)d->h + 8) * d->w * (nw * 128) + 65536 <= 0xFFFFFFE0l;
+    if (out != F9_FULL && !buf) return VCG_E_UNSUPPORTED;          // (a caller bands the image so that this never happens)
+    F9WinParams p;
+    p.x = (const unsigned char*)x;
+    p.wfrag = (const uint4*)wfrag;
+    p.bias = (const float*)bias;
+    p.y = (float*)y;
+    p.n = d->n;
+    p.h = d->h;
+    p.w_ = d->w;
+    p.strips = ceil_div(d->w, 64);
+    p.row0 = row0, p.rows = rows, p.y_row0 = y_row0, p.y_h = y_h;
+    // segments per column strip: the split that minimises the rows the busiest workgroup marches through -- rounds of items per
+    // workgroup x (segment height + 8 recomputed halo rows).  (Round 2 halved the height until the items filled the grid twice: 25 % halo
+    // rows at C3's shape, and at C4's 1080 items on 512 workgroups = a third round for 56 of them.)
+    {
+        long best = -1;
+        const int colstrips = p.n * p.strips;
+        for (int segs = 1; segs <= ceil_div(rows, 16); ++segs) {
+            const int sh = ceil_div(rows, segs);
+            if (ceil_div(rows, sh) != segs) continue;                             // (the same height reached with fewer segments)
+            const long items = (long)colstrips * segs, rounds = (items + max_grid - 1) / max_grid, cost = rounds * (sh + 8);
+            if (best < 0 || cost < best) { best = cost; p.sh = sh; p.segs = segs; }
+        }
+    }
+    p.total = p.n * p.strips * p.segs;
+    p.tanh_act = tanh_act;
+    const int grid = p.total < max_grid ? p.total : max_grid;
+#define VCG_F9_LAUNCH(KERNEL, NW, ARG) do {                                                                                \
+        constexpr int lds = NW * 2 * F_ROWB + 2 * NW * 3 * 64 * 4;                                                         \
+        if (int e = vcg_allow_dyn_lds((const void*)KERNEL, lds)) return e;                                                 \
+        KERNEL<<<grid, 64 * NW, lds, stream>>>(ARG);                                                                        \
+    } while (0)
+    const F9Params& whole = p;
+    if (out == F9_WIN_F32) {
+        if (nw == 4) VCG_F9_LAUNCH((conv9x9_c256to3_bf16_kernel<true, 4, F9_WIN_F32, F9WinParams>), 4, p);
+        else VCG_F9_LAUNCH((conv9x9_c256to3_bf16_kernel<true, 2, F9_WIN_F32, F9WinParams>), 2, p);
+    } else if (out == F9_WIN_U8) {
+        if (nw == 4) VCG_F9_LAUNCH((conv9x9_c256to3_bf16_kernel<true, 4, F9_WIN_U8, F9WinParams>), 4, p);
+        else VCG_F9_LAUNCH((conv9x9_c256to3_bf16_kernel<true, 2, F9_WIN_U8, F9WinParams>), 2, p);
+    } else if (nw == 4) {
+        if (buf) VCG_F9_LAUNCH((conv9x9_c256to3_bf16_kernel<true, 4>), 4, whole); else VCG_F9_LAUNCH((conv9x9_c256to3_bf16_kernel<false, 4>), 4, whole);
+    } else {
+        if (buf) VCG_F9_LAUNCH((conv9x9_c256to3_bf16_kernel<true, 2>), 2, whole); else VCG_F9_LAUNCH((conv9x9_c256to3_bf16_kernel<false, 2>), 2, whole);
+    }
+#undef VCG_F9_LAUNCH
+    VCG_LAUNCH_CHECK();
+    return VCG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -306,47 +406,21 @@ int vcg_conv9x9_to3_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* 
     VCG_CHECK_PTR(x);
     VCG_CHECK_PTR(wfrag);
     VCG_CHECK_PTR(y);
-    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->oh != d->h || d->ow != d->w) return VCG_E_SHAPE;
-    if ((d->cin != 256 && d->cin != 128) || d->cout != 3 || d->kh != 9 || d->kw != 9 || d->stride != 1 || d->pad_top != 4 || d->pad_left != 4) return VCG_E_UNSUPPORTED;
-    const int nw = d->cin / 64;
-    const int max_grid = F9_MAX_GRID * 4 / nw;                    // half the threads and LDS per workgroup: twice the workgroups per CU
-    F9Params p;
-    p.x = (const unsigned char*)x;
-    p.wfrag = (const uint4*)wfrag;
-    p.bias = (const float*)bias;
-    p.y = (float*)y;
-    p.n = d->n;
-    p.h = d->h;
-    p.w_ = d->w;
-    p.strips = ceil_div(d->w, 64);
-    // segments per column strip: the split that minimises the rows the busiest workgroup marches through -- rounds of items per
-    // workgroup x (segment height + 8 recomputed halo rows).  (Round 2 halved the height until the items filled the grid twice: 25 % halo
-    // rows at C3's shape, and at C4's 1080 items on 512 workgroups = a third round for 56 of them.)
-    {
-        long best = -1;
-        const int colstrips = p.n * p.strips;
-        for (int segs = 1; segs <= ceil_div(d->h, 16); ++segs) {
-            const int sh = ceil_div(d->h, segs);
-            if (ceil_div(d->h, sh) != segs) continue;                             // (the same height reached with fewer segments)
-            const long items = (long)colstrips * segs, rounds = (items + max_grid - 1) / max_grid, cost = rounds * (sh + 8);
-            if (best < 0 || cost < best) { best = cost; p.sh = sh; p.segs = segs; }
-        }
-    }
-    p.total = p.n * p.strips * p.segs;
-    p.tanh_act = tanh_act;
-    const int grid = p.total < max_grid ? p.total : max_grid;
-    // the descriptor form needs the image, four rows above and four below it inside 32-bit offsets
-    const bool buf = ((long)d->h + 8) * d->w * (nw * 128) + 65536 <= 0xFFFFFFE0l;
-#define VCG_F9_LAUNCH(BUF, NW) do {                                                                                        \
-        constexpr int lds = NW * 2 * F_ROWB + 2 * NW * 3 * 64 * 4;                                                         \
-        if (int e = vcg_allow_dyn_lds((const void*)conv9x9_c256to3_bf16_kernel<BUF, NW>, lds)) return e;                  \
-        conv9x9_c256to3_bf16_kernel<BUF, NW><<<grid, 64 * NW, lds, stream>>>(p);                                           \
-    } while (0)
-    if (nw == 4) { if (buf) VCG_F9_LAUNCH(true, 4); else VCG_F9_LAUNCH(false, 4); }
-    else { if (buf) VCG_F9_LAUNCH(true, 2); else VCG_F9_LAUNCH(false, 2); }
-#undef VCG_F9_LAUNCH
-    VCG_LAUNCH_CHECK();
-    return VCG_OK;
+    if (int e = f9_check_desc(d)) return e;
+    return f9_launch(d, x, wfrag, bias, tanh_act, y, F9_FULL, 0, d->h, 0, d->h, stream);
+}
+
+int vcg_conv9x9_to3_bf16_fwd_window(const vcg_conv_desc* d, const void* x, const void* wfrag, const void* bias, int32_t tanh_act,
+                                    int32_t out_kind, void* y, int32_t row0, int32_t rows, int32_t y_row0, int32_t y_h, hipStream_t stream) {
+    VCG_CHECK_PTR(d);
+    VCG_CHECK_PTR(x);
+    VCG_CHECK_PTR(wfrag);
+    VCG_CHECK_PTR(y);
+    if (int e = f9_check_desc(d)) return e;
+    if (rows <= 0 || row0 < 0 || (long)row0 + rows > d->h || y_row0 < 0 || (long)y_row0 + rows > y_h) return VCG_E_SHAPE;
+    if (int e = f9_check_desc(d)) return e;
+    if (out_kind != VCG_OUT_F32_NCHW && out_kind != VCG_OUT_U8_NHWC) return VCG_E_UNSUPPORTED;
+    return f9_launch(d, x, wfrag, bias, tanh_act, y, out_kind == VCG_OUT_U8_NHWC ? F9_WIN_U8 : F9_WIN_F32, row0, rows, y_row0, y_h, stream);
 }
 
 }  // extern "C"

@@ -12,7 +12,8 @@ BatchNormalization layers in inference mode.  Here that pass is
                 conv 3x3 + BN + Add           same kernel, residual operand = block input
     prefinal conv 3x3 + BN + Add(long skip)   same kernel
     upsampling: ConvT 3x3 s2 64->256 + LReLU  vcg_conv_transpose2d_bf16_fwd
-    final/conv 9x9 256->3 + tanh              vcg_conv9x9_to3_bf16_fwd (fp32 NCHW out)
+    final/conv 9x9 256->3 + tanh              vcg_conv9x9_to3_bf16_fwd (fp32 NCHW out), or vcg_conv9x9_to3_bf16_fwd_window
+                                              (a window of rows; fp32 NCHW or uint8 NHWC frames out)
 
 The 5x5 trunk convolutions run on the same entry point (the generic kernels' plan, weights as their MFMA fragments), and the
 up-sampling stages that convt3x3_c64 does not serve -- 5x5, and 3x3 on 256 channels -- on vcg_conv_transpose2d_nhwc_bf16_fwd,
@@ -21,7 +22,18 @@ topology, recorded once per input shape into a hipGraph and replayed per batch. 
 accumulation and the epilogue arithmetic fp32; the weights are rounded to bf16 once, when the engine is built or
 ``refresh()`` is called after a weight update.  The folded BatchNormalization parameters
 (scale = gamma / sqrt(moving_var + 1e-3), shift = (bias - moving_mean) * scale + beta) are 64-element fp32 vectors
-derived by vcg_axpby + vcg_norm_finalize when the engine is built or refreshed."""
+derived by vcg_axpby + vcg_norm_finalize when the engine is built or refreshed.
+
+Frames in and out.  ``predict`` / ``replay`` take and return fp32 (numpy NHWC / device NCHW in [-1, 1]) as the reference's
+``upscaler.predict`` does.  ``upscale_frames`` is the reference's whole inference path, convert_image_series_to_array -> predict ->
+convert_array_to_image (data.py:253-270, 358-363): uint8 frames in, uint8 frames out.  One byte per sample crosses the bus each way:
+vcg_frames_u8_to_nchw fills the captured graph's input on the device, and final/conv stores the uint8 NHWC frame itself.
+
+Row bands.  Every kernel of the tail (the up-sampling stages and final/conv) uses 32-bit offsets inside a launch, so a launch's largest
+tensor must stay below 4 GiB.  Where one frame's does not (540x1024 -> 2160x4096: 4.53 GB; 2160x3840 still fits), the tail runs on row
+bands of the trunk's output (``band_plan``): the transposed convolutions unchanged on a band extended by the halo its window needs, final/conv on the
+window of the band's rows that are right."""
+import collections
 import ctypes
 import os
 
@@ -32,7 +44,98 @@ from . import _engine as E
 from . import _lib as L
 
 
+TAIL_LIMIT = 0xFFFFFFE0          # bytes of a tail launch's largest tensor: the kernels' offsets are 32-bit inside a launch
+
+# A band of the tail: low-res rows [ia, ib) of the trunk's output, extended to [start, end) (clipped to the image) so that the window's
+# rows and their 4-row halo are right; the final launch computes rows [row0, row0 + rows) of the band's up-sampled rows and stores them as
+# rows [y_row0, y_row0 + rows) of the frame.
+Band = collections.namedtuple("Band", "ia ib start end row0 rows y_row0")
+
+
+def tail_halo(k, n_stages):
+    """(e_top, e_bot): the low-res rows above / below its own that a band needs.  final/conv reads 4 rows above and below a window; output
+    row o of a TF-SAME Conv2DTranspose(k, strides 2) with crop = max(k - 2, 0) // 2 reads input rows ceil((o + crop - k + 1) / 2) ...
+    floor((o + crop) / 2).  Run back from a window [f * ia, f * ib) through the stages: every coordinate is (a multiple of the remaining
+    factor) * ia + a constant, so the recursion on the constants alone (ia = ib = 0) gives the halo of every band."""
+    crop = max(k - 2, 0) // 2
+    lo, hi = -4, 3                       # first / last row read around the window [0, 0): rows -4 .. -1 above it, 0 .. 3 below
+    for _ in range(n_stages):
+        lo = -((-(lo + crop - k + 1)) // 2)
+        hi = (hi + crop) // 2
+    return -lo, hi + 1
+
+
+def band_plan(h, k, n_stages, band_rows=None):
+    """The bands of a frame of h low-res rows: band_rows rows each (the last one shorter); None: one band."""
+    if band_rows is not None and int(band_rows) < 1:
+        raise ValueError("band_rows must be a positive number of low-res rows, got %r" % (band_rows,))
+    f = 2 ** n_stages
+    e_top, e_bot = tail_halo(k, n_stages)
+    step = h if band_rows is None else min(int(band_rows), h)
+    bands = []
+    for ia in range(0, h, step):
+        ib = min(ia + step, h)
+        start, end = max(0, ia - e_top), min(h, ib + e_bot)
+        bands.append(Band(ia, ib, start, end, f * (ia - start), f * (ib - ia), f * ia))
+    return bands
+
+
+def band_bytes(band, w, n_stages, channels, halo_rows=0):
+    """bytes of the largest tensor of one frame's band: the last stage's output, plus halo_rows rows (final/conv's descriptor covers 4 rows
+    above and 4 below the band it reads)"""
+    f = 2 ** n_stages
+    return (f * (band.end - band.start) + halo_rows) * f * w * channels * 2
+
+
+def _fits(band, w, n_stages, channels, limit, windowed):
+    """does one frame's band fit the tail's launches: the transposed convolutions' tensors, and for the window launch of final/conv its
+    descriptor (band + 8 rows + 64 KiB, vcg_conv9x9_to3_bf16_fwd_window)"""
+    if windowed:
+        return band_bytes(band, w, n_stages, channels, 8) + 65536 <= limit
+    return band_bytes(band, w, n_stages, channels) <= limit
+
+
+def tail_chunk(n, h, w, n_stages, channels=256, limit=TAIL_LIMIT, legacy=False):
+    """frames per launch of an unbanded tail: as many as keep the last stage's output within the limit, spread evenly over the launches"""
+    if legacy:
+        return n
+    f = 2 ** n_stages
+    per = f * f * h * w * channels * 2
+    ch = max(1, min(n, limit // per))
+    launches = -(-n // ch)
+    return -(-n // launches)                 # the same number of launches, frames spread evenly (32 -> 16 + 16, not 31 + 1)
+
+
+def tail_plan(n, h, w, k, n_stages, band_rows=None, channels=256, limit=TAIL_LIMIT, legacy=False, windowed=False):
+    """(frames per launch, bands) of the tail for n frames of h x w low-res pixels.
+    band_rows None: one band wherever one frame's tail fits the limit, with the frames per launch tail_chunk gives (the k3 x2 topology: all
+    of them, its launch sequence unchanged); otherwise the fewest equal bands whose largest tensor fits at one frame per launch.  An
+    integer forces bands of that many low-res rows.
+    windowed: a single band goes through final/conv's window launch too (uint8 output) and has to fit its descriptor."""
+    if band_rows is not None:
+        bands = band_plan(h, k, n_stages, band_rows)
+    else:
+        bands = band_plan(h, k, n_stages, None)
+        if not _fits(bands[0], w, n_stages, channels, limit, windowed):
+            for nb in range(2, h + 1):
+                bands = band_plan(h, k, n_stages, -(-h // nb))
+                if all(_fits(b, w, n_stages, channels, limit, True) for b in bands):
+                    break
+            else:
+                raise ValueError("a band of one low-res row of width %d exceeds the tail's limit of %d bytes" % (w, limit))
+    if len(bands) == 1:
+        if windowed and not _fits(bands[0], w, n_stages, channels, limit, True):
+            raise ValueError("band_rows=%r: the band exceeds the tail's limit of %d bytes" % (band_rows, limit))
+        return tail_chunk(n, h, w, n_stages, channels, limit, legacy), bands
+    if not all(_fits(b, w, n_stages, channels, limit, True) for b in bands):
+        raise ValueError("band_rows=%r: a band's largest tensor exceeds the tail's limit of %d bytes" % (band_rows, limit))
+    ch = max(1, min(n, limit // max(band_bytes(b, w, n_stages, channels) for b in bands)))
+    launches = -(-n // ch)
+    return -(-n // launches), bands
+
+
 class Bf16Generator:
+    TAIL_LIMIT = TAIL_LIMIT    # a test can lower it on an instance to force automatic banding at a small shape
     TAIL_CHANNELS = 256        # channels of the up-sampling stages' outputs (model.py:288): what the 4 GiB rule of _tail_chunk counts
 
     def __init__(self, model):
@@ -103,36 +206,60 @@ class Bf16Generator:
         self.first = (E.pack_first9x9_bf16(rt, m.c_init.ps[m.c_init.name + "/kernel"]), m.c_init.ps[m.c_init.name + "/bias"],
                       m.c_init.ps[m.a_init.prelu_name + "/alpha"])
         self._graphs.clear()          # recorded graphs hold the old parameter buffers
+        self._staging = None          # upscale_frames' pinned and device staging buffers
 
     # ---- one forward pass (22 launches) -----------------------------------------------------------------------
-    def _buffers(self, n, h, w):
-        key = (n, h, w)
+    def _trunk_buffers(self, n, h, w):
+        key = ("trunk", n, h, w)
         if key not in self._bufs:
             dev = self.rt.device
             bf = lambda c, hh, ww: torch.empty(n, hh, ww, c, dtype=torch.bfloat16, device=dev)
+            self._bufs[key] = {"skip": bf(64, h, w),
+                               "a": bf(64, h, w), "b": bf(64, h, w), "c": bf(64, h, w),
+                               "z": bf(64, h, w) if self.instance else None,
+                               "stats": torch.empty(5, n * 64, dtype=torch.float32, device=dev) if self.instance else None}
+        return self._bufs[key]
+
+    def _buffers(self, n, h, w):
+        """the trunk's buffers and those of the unbanded fp32 tail"""
+        key = (n, h, w)
+        if key not in self._bufs:
+            dev = self.rt.device
             ch = self._tail_chunk(n, h, w)
             f = 2 ** len(self.ups)
             # one bf16 NHWC buffer per up-sampling stage: [ch, 2h, 2w, 256], [ch, 4h, 4w, 256], ...
             us = [torch.empty(ch, 2 ** (s + 1) * h, 2 ** (s + 1) * w, 256, dtype=torch.bfloat16, device=dev) for s in range(len(self.ups))]
-            self._bufs[key] = {"skip": bf(64, h, w),
-                               "a": bf(64, h, w), "b": bf(64, h, w), "c": bf(64, h, w),
-                               "u": us[0], "us": us,
-                               "z": bf(64, h, w) if self.instance else None,
-                               "stats": torch.empty(5, n * 64, dtype=torch.float32, device=dev) if self.instance else None,
-                               "y": torch.empty(n, 3, f * h, f * w, dtype=torch.float32, device=dev)}
+            self._bufs[key] = dict(self._trunk_buffers(n, h, w), u=us[0], us=us,
+                                   y=torch.empty(n, 3, f * h, f * w, dtype=torch.float32, device=dev))
+        return self._bufs[key]
+
+    def _band_buffers(self, n, h, w, ch, bands, out_kind):
+        """the banded (or uint8) tail: flat buffers sized for the largest band of ch frames -- the band's rows of the trunk output and one
+        per up-sampling stage, viewed per band as compact [c, rows, w, C] tensors -- and the frames it writes"""
+        key = (n, h, w, ch, tuple(bands), out_kind)
+        if key not in self._bufs:
+            dev = self.rt.device
+            f = 2 ** len(self.ups)
+            rows = max(b.end - b.start for b in bands)
+            part = max([b.end - b.start for b in bands if b.end - b.start < h] or [0])      # (a band of all rows reads the trunk output in place)
+            flat = lambda count: torch.empty(count, dtype=torch.bfloat16, device=dev)
+            y = (torch.empty(n, f * h, f * w, 3, dtype=torch.uint8, device=dev) if out_kind == L.OUT_U8_NHWC
+                 else torch.empty(n, 3, f * h, f * w, dtype=torch.float32, device=dev))
+            self._bufs[key] = {"in": flat(ch * part * w * 64) if part else None,
+                               "us": [flat(ch * 4 ** (s + 1) * rows * w * 256) for s in range(len(self.ups))], "y": y}
         return self._bufs[key]
 
     def _tail_chunk(self, n, h, w):
-        """frames per launch of the up-sampling stages and final/conv.  Beyond the k3 x2 topology, a launch's largest tensor (the
-        last stage's output, 2 * 256 bytes per pixel) stays below 4 GiB: the kernels' offsets are 32-bit inside an image, and final/conv's
-        descriptor covers the whole launch"""
-        if self.legacy:
-            return n
-        f = 2 ** len(self.ups)
-        per = f * f * h * w * self.TAIL_CHANNELS * 2
-        ch = max(1, min(n, 0xFFFFFFE0 // per))
-        launches = -(-n // ch)
-        return -(-n // launches)                 # the same number of launches, frames spread evenly (32 -> 16 + 16, not 31 + 1)
+        """frames per launch of the up-sampling stages and final/conv of an unbanded tail.  Beyond the k3 x2 topology, a launch's largest
+        tensor (the last stage's output, 2 * 256 bytes per pixel) stays below 4 GiB: the kernels' offsets are 32-bit inside an image, and
+        final/conv's descriptor covers the whole launch"""
+        return tail_chunk(n, h, w, len(self.ups), self.TAIL_CHANNELS, self.TAIL_LIMIT, self.legacy)
+
+    def _plan(self, n, h, w, band_rows=None, out_kind=L.OUT_F32_NCHW):
+        """(frames per launch, bands) of the tail; one band and fp32 output is the path without bands, with _tail_chunk's frames per launch"""
+        ch, bands = tail_plan(n, h, w, self.k, len(self.ups), band_rows, self.TAIL_CHANNELS, self.TAIL_LIMIT, self.legacy,
+                              windowed=out_kind != L.OUT_F32_NCHW)
+        return ch, tuple(bands)
 
     def _conv(self, x, w, y, scale, shift, act, alpha, res, n, h, wd):
         rt = self.rt
@@ -148,13 +275,13 @@ class Bf16Generator:
     def _conv_instance_norm(self, x, w, y, bias, act, alpha, res, n, h, wd):
         """conv (+bias) -> per-image statistics -> normalise + activation + Add, all on bf16 NHWC"""
         rt = self.rt
-        z = self._buffers(n, h, wd)["z"]
+        z = self._trunk_buffers(n, h, wd)["z"]
         k = self.k
         d = L.ConvDesc(n, 64, h, wd, 64, h, wd, k, k, 1, k // 2, k // 2)
         ep = L.EpilogueBf16(None, bias.data_ptr(), L.ACT_NONE, 0.0, None, None)
         L.check(rt.lib.vcg_conv2d_bf16_fwd(ctypes.byref(d), x.data_ptr(), w.data_ptr(), z.data_ptr(), ctypes.byref(ep), rt.stream),
                 "vcg_conv2d_bf16_fwd")
-        st = self._buffers(n, h, wd)["stats"]
+        st = self._trunk_buffers(n, h, wd)["stats"]
         mean, var, scale, shift, invstd = (st[i] for i in range(5))
         ws, wsn = rt.workspace(rt.lib.vcg_norm_stats_bf16_workspace_bytes(n, 64, h * wd, L.NORM_INSTANCE))
         L.check(rt.lib.vcg_norm_stats_bf16(z.data_ptr(), n, 64, h * wd, L.NORM_INSTANCE, mean.data_ptr(), var.data_ptr(), ws, wsn,
@@ -166,11 +293,14 @@ class Bf16Generator:
                                              res.data_ptr() if res is not None else None, y.data_ptr(), rt.stream),
                 "vcg_norm_act_fwd_bf16")
 
-    def forward(self, x):
-        """x: device fp32 NCHW [n,3,h,w] in [-1,1] -> device fp32 NCHW [n,3,f*h,f*w] (f = upscale_factor; buffer owned by the engine)"""
-        rt, m = self.rt, self.model
+    def forward(self, x, out_kind=L.OUT_F32_NCHW, band_rows=None):
+        """x: device fp32 NCHW [n,3,h,w] in [-1,1] -> device fp32 NCHW [n,3,f*h,f*w], or with out_kind OUT_U8_NHWC device uint8 frames
+        [n,f*h,f*w,3] (f = upscale_factor; buffer owned by the engine).  band_rows: see tail_plan"""
+        rt = self.rt
         n, _, h, w = x.shape
-        B = self._buffers(n, h, w)
+        ch, bands = self._plan(n, h, w, band_rows, out_kind)
+        banded = len(bands) > 1 or out_kind != L.OUT_F32_NCHW
+        B = self._trunk_buffers(n, h, w) if banded else self._buffers(n, h, w)
         w0, b0, a0 = self.first
         d0 = L.ConvDesc(n, 3, h, w, 64, h, w, 9, 9, 1, 4, 4)
         L.check(rt.lib.vcg_conv9x9_from3_bf16_fwd(ctypes.byref(d0), x.data_ptr(), w0.data_ptr(), b0.data_ptr(), a0.data_ptr(),
@@ -184,60 +314,164 @@ class Bf16Generator:
         wp, sp, hp = self.prefinal
         out = B["a"] if cur is not B["a"] else B["c"]
         self._conv(cur, wp, out, sp, hp, L.ACT_NONE, None, B["skip"], n, h, w)
+        if banded:
+            return self._tail_bands(out, n, h, w, ch, bands, out_kind)
         wf, bf_ = self.final
-        k, crop = self.k, max(self.k - 2, 0) // 2           # TF-SAME crop of Conv2DTranspose(k, strides 2): k3 (0, 1), k5 (1, 2)
         us, y = B["us"], B["y"]
         ch = us[0].shape[0]
         for i in range(0, n, ch):
             c = min(ch, n - i)
-            src, hh, ww = out[i:i + c], h, w
-            for (wt, bt, slope, cin), up, u in zip(self.ups, m.ups, us):
-                dt = L.ConvDesc(c, cin, hh, ww, 256, 2 * hh, 2 * ww, k, k, 2, crop, crop)
-                if self._generic(up, 0):
-                    L.check(rt.lib.vcg_conv_transpose2d_nhwc_bf16_fwd(ctypes.byref(dt), src.data_ptr(), wt.data_ptr(), bt.data_ptr(), L.ACT_LRELU,
-                                                                      slope, u.data_ptr(), rt.stream), "vcg_conv_transpose2d_nhwc_bf16_fwd")
-                else:
-                    ept = L.EpilogueBf16(None, bt.data_ptr(), L.ACT_LRELU, slope, None, None)
-                    L.check(rt.lib.vcg_conv_transpose2d_bf16_fwd(ctypes.byref(dt), src.data_ptr(), wt.data_ptr(), u.data_ptr(), ctypes.byref(ept),
-                                                                 rt.stream), "vcg_conv_transpose2d_bf16_fwd")
-                src, hh, ww = u, 2 * hh, 2 * ww
+            src, hh, ww = self._upsample(out[i:i + c], us, c, h, w)
             df = L.ConvDesc(c, 256, hh, ww, 3, hh, ww, 9, 9, 1, 4, 4)
             L.check(rt.lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, y[i:i + c].data_ptr(),
                                                     rt.stream), "vcg_conv9x9_to3_bf16_fwd")
         return B["y"]
 
+    def _upsample(self, src, us, c, hh, ww):
+        """the up-sampling stages on c frames of hh x ww pixels (a whole image or a band: a band is a shorter image) into the buffers us;
+        returns the last stage's output and its size"""
+        rt, k, crop = self.rt, self.k, max(self.k - 2, 0) // 2           # TF-SAME crop of Conv2DTranspose(k, strides 2): k3 (0, 1), k5 (1, 2)
+        for (wt, bt, slope, cin), up, u in zip(self.ups, self.model.ups, us):
+            dt = L.ConvDesc(c, cin, hh, ww, 256, 2 * hh, 2 * ww, k, k, 2, crop, crop)
+            if self._generic(up, 0):
+                L.check(rt.lib.vcg_conv_transpose2d_nhwc_bf16_fwd(ctypes.byref(dt), src.data_ptr(), wt.data_ptr(), bt.data_ptr(), L.ACT_LRELU,
+                                                                  slope, u.data_ptr(), rt.stream), "vcg_conv_transpose2d_nhwc_bf16_fwd")
+            else:
+                ept = L.EpilogueBf16(None, bt.data_ptr(), L.ACT_LRELU, slope, None, None)
+                L.check(rt.lib.vcg_conv_transpose2d_bf16_fwd(ctypes.byref(dt), src.data_ptr(), wt.data_ptr(), u.data_ptr(), ctypes.byref(ept),
+                                                             rt.stream), "vcg_conv_transpose2d_bf16_fwd")
+            src, hh, ww = u, 2 * hh, 2 * ww
+        return src, hh, ww
+
+    def _tail_bands(self, out, n, h, w, ch, bands, out_kind):
+        """the tail band by band: the band's rows of the trunk output in a compact buffer (a strided copy: 64 channels at low resolution),
+        the up-sampling stages unchanged on the band, final/conv on the band's window into its rows of the frames"""
+        rt = self.rt
+        T = self._band_buffers(n, h, w, ch, bands, out_kind)
+        wf, bf_ = self.final
+        f, y = 2 ** len(self.ups), T["y"]
+        for i in range(0, n, ch):
+            c = min(ch, n - i)
+            for b in bands:
+                rows = b.end - b.start
+                if rows == h:
+                    src = out[i:i + c]
+                else:
+                    src = T["in"][:c * rows * w * 64].view(c, rows, w, 64)
+                    src.copy_(out[i:i + c, b.start:b.end])
+                us = [u[:c * 4 ** (s + 1) * rows * w * 256].view(c, 2 ** (s + 1) * rows, 2 ** (s + 1) * w, 256) for s, u in enumerate(T["us"])]
+                src, hh, ww = self._upsample(src, us, c, rows, w)
+                df = L.ConvDesc(c, 256, hh, ww, 3, hh, ww, 9, 9, 1, 4, 4)
+                L.check(rt.lib.vcg_conv9x9_to3_bf16_fwd_window(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, out_kind,
+                                                               y[i:i + c].data_ptr(), b.row0, b.rows, b.y_row0, f * h, rt.stream),
+                        "vcg_conv9x9_to3_bf16_fwd_window")
+        return y
+
     # ---- hipGraph ---------------------------------------------------------------------------------------------
-    def capture(self, n, h, w):
-        """record the pass for one input shape; ``replay(x)`` then costs one graph launch"""
-        key = (n, h, w)
+    def capture(self, n, h, w, out_kind=L.OUT_F32_NCHW, band_rows=None):
+        """record the pass for one input shape, output kind and band plan; ``replay(x)`` then costs one graph launch"""
+        key = (n, h, w, out_kind) + self._plan(n, h, w, band_rows, out_kind)
         if key in self._graphs:
             return self._graphs[key]
         xin = torch.zeros(n, 3, h, w, dtype=torch.float32, device=self.rt.device)
-        self.forward(xin)                  # warm-up: buffers exist, kernel attributes are set
+        self.forward(xin, out_kind, band_rows)                  # warm-up: buffers exist, kernel attributes are set
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            y = self.forward(xin)
+            y = self.forward(xin, out_kind, band_rows)
         self._graphs[key] = (g, xin, y)
         return self._graphs[key]
 
-    def replay(self, x):
-        g, xin, y = self.capture(*[x.shape[0], x.shape[2], x.shape[3]])
+    def replay(self, x, band_rows=None):
+        g, xin, y = self.capture(x.shape[0], x.shape[2], x.shape[3], L.OUT_F32_NCHW, band_rows)
         xin.copy_(x)
         g.replay()
         return y
 
     # ---- Keras-style entry point -------------------------------------------------------------------------------
-    def predict(self, x, batch_size=32):
-        """x: numpy NHWC in [-1,1] (data.py:266-270) -> numpy NHWC float32, through the captured graph"""
+    def predict(self, x, batch_size=32, band_rows=None):
+        """x: numpy NHWC in [-1,1] (data.py:266-270) -> numpy NHWC float32, through the captured graph.  band_rows: low-res rows per
+        band of the tail (tail_plan); None bands a frame only where its tail exceeds the 4 GiB of a launch"""
         rt = self.rt
         x = np.asarray(x)
         outs = []
         for i in range(0, x.shape[0], batch_size):
             xb = E.to_device_nchw(rt, x[i:i + batch_size])
-            y = self.replay(xb)
+            y = self.replay(xb, band_rows)
             outs.append(E.to_nhwc(rt, y).cpu().numpy())
         return np.concatenate(outs, 0)
+
+    # ---- uint8 frames in, uint8 frames out ----------------------------------------------------------------------
+    def upscale_frames(self, frames, batch_size=32, band_rows=None):
+        """frames: uint8 [N,h,w,3] (numpy, torch, or a list of HxWx3 images) -> uint8 numpy [N,f*h,f*w,3]: the reference's
+        convert_image_series_to_array -> predict -> convert_array_to_image (data.py:253-270, 358-363).  Per batch the uint8 frames go to
+        the device (1 byte per sample), vcg_frames_u8_to_nchw writes the captured graph's input, the graph is replayed -- final/conv stores
+        the uint8 NHWC frames -- and the uint8 result comes back.  A ragged last batch records its own graph, as in predict.
+        Batch i+1's upload and batch i-1's download run under batch i's replay: two pinned host staging buffers and two device buffers
+        per direction, one copy stream per direction, events only (1.16x the rate of copying synchronously on the compute stream at
+        256 -> 512; scripts/bench_infer_bf16.py --u8, profiles/upscale_frames.txt).  The graph's input and output are touched by the
+        compute stream alone (the conversion kernel writes the input, a device copy takes the output), in stream order.  The staging
+        buffers of the last (batch, h, w) are kept until refresh()."""
+        rt = self.rt
+        if isinstance(frames, torch.Tensor):
+            t = frames
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(frames)))
+        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3:
+            raise ValueError("expected uint8 frames [N,h,w,3], got %s %s" % (t.dtype, tuple(t.shape)))
+        n, h, w, _ = t.shape
+        f = 2 ** len(self.ups)
+        out = np.empty((n, f * h, f * w, 3), dtype=np.uint8)
+        if n == 0:
+            return out
+        bs = min(batch_size, n)
+        key = (bs, h, w)
+        if self._staging is None or self._staging["key"] != key:
+            dev = rt.device
+            self._staging = {"key": key,
+                             "hin": [torch.empty(bs, h, w, 3, dtype=torch.uint8, pin_memory=True) for _ in range(2)],
+                             "hout": [torch.empty(bs, f * h, f * w, 3, dtype=torch.uint8, pin_memory=True) for _ in range(2)],
+                             "din": [torch.empty(bs, h, w, 3, dtype=torch.uint8, device=dev) for _ in range(2)],
+                             "dout": [torch.empty(bs, f * h, f * w, 3, dtype=torch.uint8, device=dev) for _ in range(2)],
+                             "up": torch.cuda.Stream(), "dn": torch.cuda.Stream()}
+        S = self._staging
+        starts = list(range(0, n, bs))
+        for nb in {min(bs, n - i) for i in starts}:
+            self.capture(nb, h, w, L.OUT_U8_NHWC, band_rows)             # graphs are recorded before the pipeline starts
+        main = torch.cuda.current_stream()
+        ev = lambda: [torch.cuda.Event(), torch.cuda.Event()]
+        up_done, in_used, y_taken, dn_done = ev(), ev(), ev(), ev()
+        for j in range(len(starts) + 1):
+            if j < len(starts):
+                i, s = starts[j], j % 2
+                nb = min(bs, n - i)
+                if j >= 2:
+                    up_done[s].synchronize()                             # the staging buffer's previous upload has left it
+                S["hin"][s][:nb].copy_(t[i:i + nb])
+                with torch.cuda.stream(S["up"]):
+                    if j >= 2:
+                        S["up"].wait_event(in_used[s])                   # the conversion of batch j-2 has read din[s]
+                    S["din"][s][:nb].copy_(S["hin"][s][:nb], non_blocking=True)
+                    up_done[s].record(S["up"])
+                g, xin, y = self.capture(nb, h, w, L.OUT_U8_NHWC, band_rows)
+                main.wait_event(up_done[s])
+                L.check(rt.lib.vcg_frames_u8_to_nchw(S["din"][s].data_ptr(), xin.data_ptr(), nb, h, w, 3, rt.stream), "vcg_frames_u8_to_nchw")
+                in_used[s].record(main)
+                g.replay()
+                if j >= 2:
+                    main.wait_event(dn_done[s])                          # the download of batch j-2 has read dout[s]
+                S["dout"][s][:nb].copy_(y)
+                y_taken[s].record(main)
+                with torch.cuda.stream(S["dn"]):
+                    S["dn"].wait_event(y_taken[s])
+                    S["hout"][s][:nb].copy_(S["dout"][s][:nb], non_blocking=True)
+                    dn_done[s].record(S["dn"])
+            if j >= 1:
+                i, s = starts[j - 1], (j - 1) % 2
+                nb = min(bs, n - i)
+                dn_done[s].synchronize()
+                out[i:i + nb] = S["hout"][s][:nb].numpy()
+        return out
 
 
 class Bf16AttentionGenerator(Bf16Generator):
@@ -253,12 +487,17 @@ class Bf16AttentionGenerator(Bf16Generator):
             sigmoid(conv(u)) * m                                vcg_conv_in_gate_bf16_fwd (cin 6)
             ConvT k s2 -> 128 + LeakyReLU(0.2)                  vcg_conv_transpose2d_nhwc_bf16_fwd
             + ConvT(s+1, strides s)(atanh(0.99999 frames))      vcg_input_convt_add_bf16, in place
-        final/conv 9x9 128->3 + tanh                            vcg_conv9x9_to3_bf16_fwd (cin 128)
+        final/conv 9x9 128->3 + tanh                            vcg_conv9x9_to3_bf16_fwd (cin 128), or its window form for uint8 frames
 
-    3 launches per residual block; _fold, _pack, capture / replay / predict and the 4 GiB chunking of the tail are Bf16Generator's."""
+    3 launches per residual block; _fold, _pack, capture / replay / predict / upscale_frames and the 4 GiB chunking of the tail are
+    Bf16Generator's.  The tail is not banded: it reads fp32 NCHW frame data (the gates' inputs, to_add_input) whose row bands are not
+    contiguous, and its largest tensor has 128 channels, so a whole 4K frame fits a launch."""
     TAIL_CHANNELS = 128
     SERVED = "bf16 inference of make_upscaler_attention is instantiated for filters=64 on 3-channel (RGB) frames, norm='batch', " \
              "kernel_size 3 or 5 and upscale_factor 2 or 4 (any res_block_num); use model.predict for other shapes"
+    SERVED_TAIL = "bf16 inference of make_upscaler_attention runs the tail on whole frames (band_rows=None) whose largest tensor, " \
+                  "f*h x f*w x 128 channels in bf16, fits a launch of 4 GiB (a 2160x3840 frame does); row bands are served for " \
+                  "make_upscaler_orig models only"
 
     def __init__(self, model):
         cfg = getattr(model, "attention_generator", None)
@@ -315,6 +554,7 @@ class Bf16AttentionGenerator(Bf16Generator):
         c0 = ly["initial/conv"]
         self.first = (E.pack_first9x9_bf16(rt, ps[c0.name + "/kernel"]), ps[c0.name + "/bias"], ps["initial/prelu/alpha"])
         self._graphs.clear()          # recorded graphs hold the old parameter buffers
+        self._staging = None          # upscale_frames' pinned and device staging buffers
 
     def _buffers(self, n, h, w):
         key = (n, h, w)
@@ -334,16 +574,26 @@ class Bf16AttentionGenerator(Bf16Generator):
                                "y": torch.empty(n, 3, f * h, f * w, dtype=torch.float32, device=dev)}
         return self._bufs[key]
 
+    def _plan(self, n, h, w, band_rows=None, out_kind=L.OUT_F32_NCHW):
+        if band_rows is not None:
+            raise NotImplementedError(self.SERVED_TAIL)
+        one = band_plan(h, self.k, len(self.ups), None)
+        if not _fits(one[0], w, len(self.ups), self.TAIL_CHANNELS, self.TAIL_LIMIT, out_kind != L.OUT_F32_NCHW):
+            raise NotImplementedError(self.SERVED_TAIL)
+        return self._tail_chunk(n, h, w), tuple(one)
+
     def _gate(self, gate, u, cin, m, y, n, h, w):
         (wg, bg), k, rt = gate, self.k, self.rt
         d = L.ConvDesc(n, cin, h, w, m.shape[3], h, w, k, k, 1, k // 2, k // 2)
         L.check(rt.lib.vcg_conv_in_gate_bf16_fwd(ctypes.byref(d), u.data_ptr(), wg.data_ptr(), bg.data_ptr(), m.data_ptr(), y.data_ptr(), rt.stream),
                 "vcg_conv_in_gate_bf16_fwd")
 
-    def forward(self, x):
-        """x: device fp32 NCHW [n,3,h,w] in [-1,1] -> device fp32 NCHW [n,3,f*h,f*w] (f = upscale_factor; buffer owned by the engine)"""
+    def forward(self, x, out_kind=L.OUT_F32_NCHW, band_rows=None):
+        """x: device fp32 NCHW [n,3,h,w] in [-1,1] -> device fp32 NCHW [n,3,f*h,f*w], or with out_kind OUT_U8_NHWC device uint8 frames
+        [n,f*h,f*w,3] (f = upscale_factor; buffer owned by the engine)"""
         rt = self.rt
         n, _, h, w = x.shape
+        self._plan(n, h, w, band_rows, out_kind)          # refuses what the tail does not serve
         B = self._buffers(n, h, w)
         w0, b0, a0 = self.first
         d0 = L.ConvDesc(n, 3, h, w, 64, h, w, 9, 9, 1, 4, 4)
@@ -370,7 +620,13 @@ class Bf16AttentionGenerator(Bf16Generator):
                 L.check(rt.lib.vcg_copy_channels(src.data_ptr(), st["u"].data_ptr(), n, 3, 0, 6, off, 3, r * r * hw, rt.stream), "vcg_copy_channels")
         wf, bf_, cfin = self.final
         k, crop = self.k, max(self.k - 2, 0) // 2           # TF-SAME crop of Conv2DTranspose(k, strides 2): k3 (0, 1), k5 (1, 2)
-        y, ch = B["y"], B["chunk"]
+        ch, f = B["chunk"], 2 ** len(self.ups)
+        if out_kind == L.OUT_U8_NHWC:
+            if "y8" not in B:
+                B["y8"] = torch.empty(n, f * h, f * w, 3, dtype=torch.uint8, device=rt.device)
+            y = B["y8"]
+        else:
+            y = B["y"]
         for i in range(0, n, ch):
             c = min(ch, n - i)
             src, hh, ww = out[i:i + c], h, w
@@ -385,6 +641,10 @@ class Bf16AttentionGenerator(Bf16Generator):
                                                         rt.stream), "vcg_input_convt_add_bf16")
                 src, hh, ww = st["y"], 2 * hh, 2 * ww
             df = L.ConvDesc(c, cfin, hh, ww, 3, hh, ww, 9, 9, 1, 4, 4)
-            L.check(rt.lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, y[i:i + c].data_ptr(),
-                                                    rt.stream), "vcg_conv9x9_to3_bf16_fwd")
+            if out_kind == L.OUT_U8_NHWC:             # the whole frame as one window: final/conv stores the uint8 NHWC frames
+                L.check(rt.lib.vcg_conv9x9_to3_bf16_fwd_window(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, out_kind,
+                                                               y[i:i + c].data_ptr(), 0, hh, 0, hh, rt.stream), "vcg_conv9x9_to3_bf16_fwd_window")
+            else:
+                L.check(rt.lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, y[i:i + c].data_ptr(),
+                                                        rt.stream), "vcg_conv9x9_to3_bf16_fwd")
         return y

@@ -39,6 +39,7 @@ class EpilogueBf16(ctypes.Structure):
 
 STATS_NONE, STATS_BATCH, STATS_INSTANCE = 0, 1, 2
 E_UNSUPPORTED = -3            # VCG_E_UNSUPPORTED
+OUT_F32_NCHW, OUT_U8_NHWC = 0, 1          # VCG_OUT_*: what vcg_conv9x9_to3_bf16_fwd_window stores
 
 # name -> (restype, argtypes); every symbol include/vcg.h declares
 _P = c_void_p
@@ -146,6 +147,7 @@ SIGNATURES = {
     "vcg_conv9x9_from3_bf16_fwd": (c_int, [_D, _P, _P, _P, _P, _P, _P]),
     "vcg_pack_final9x9_bf16": (c_int, [_P, _P, _P]),
     "vcg_conv9x9_to3_bf16_fwd": (c_int, [_D, _P, _P, _P, c_int, _P, _P]),
+    "vcg_conv9x9_to3_bf16_fwd_window": (c_int, [_D, _P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P]),
     "vcg_conv9x9_to3_bf16_wfrag_bytes": (c_size_t, [c_int]),
     "vcg_pack_conv9x9_to3_bf16": (c_int, [_P, c_int, _P, _P]),
     "vcg_conv_in_gate_bf16_wfrag_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
