@@ -351,6 +351,18 @@ int vcg_pack_conv9x9_to3_bf16(const void* w, int32_t cin, void* out, hipStream_t
 #define VCG_OUT_U8_NHWC 1
 int vcg_conv9x9_to3_bf16_fwd_window(const vcg_conv_desc* d, const void* x, const void* wfrag, const void* bias, int32_t tanh_act,
                                     int32_t out_kind, void* y, int32_t row0, int32_t rows, int32_t y_row0, int32_t y_h, hipStream_t stream);
+/* head/conv of make_generator_cyclegan: the same layer on 64 input channels, under names of its own (the entry points above keep answering
+ * 0 / VCG_E_UNSUPPORTED at cin = 64).  wfrag: vcg_conv9x9_c64to3_bf16_wfrag_bytes() = (2304 + 4) * 16 bytes made by
+ * vcg_pack_conv9x9_c64to3_bf16 from Keras' (9,9,64,3) fp32 kernel.  The whole-image and the window form have the contracts of
+ * vcg_conv9x9_to3_bf16_fwd / _fwd_window: a window's rows equal the whole-image launch bit for bit, the uint8 form equals
+ * vcg_nchw_to_frames_u8 of the fp32 form, nothing outside the window's rows of y is written, no workspace.  VCG_E_UNSUPPORTED: d->cin != 64,
+ * whatever else those refuse, and -- in both forms -- an image whose (d->h + 8) * d->w * 128 bytes (+ 64 KiB) do not fit 32-bit offsets. */
+size_t vcg_conv9x9_c64to3_bf16_wfrag_bytes(void);
+int vcg_pack_conv9x9_c64to3_bf16(const void* w, void* out, hipStream_t stream);
+int vcg_conv9x9_c64to3_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* wfrag, const void* bias, int32_t tanh_act, void* y,
+                                hipStream_t stream);
+int vcg_conv9x9_c64to3_bf16_fwd_window(const vcg_conv_desc* d, const void* x, const void* wfrag, const void* bias, int32_t tanh_act,
+                                       int32_t out_kind, void* y, int32_t row0, int32_t rows, int32_t y_row0, int32_t y_h, hipStream_t stream);
 
 /* initial/conv of the generator (upscaling/upscaler/model.py:275-276): Conv2D(64, 9, 'same') + bias + PReLU from the
  * fp32 NCHW frames to bf16 NHWC -- the entry into the bf16 layout.  wfrag: VCG_FIRST9X9_WFRAG_BYTES bytes of MFMA operand

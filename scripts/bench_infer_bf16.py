@@ -6,6 +6,12 @@ batch.  Prints one JSON line per run, shaped like ``bench.py --config c5``'s.
            to_inference_bf16(); --full then times one launch of each kind the pass makes and, for the memory-bound ones (the gates,
            to_add_input), the bytes they must move per second next to vcg_norm_act_fwd_bf16 on the same tensor
 
+  --generator cyclegan    make_generator_cyclegan (_graph.py; stem 9x9 -> --n-downsample stride-2 convolutions -> residual blocks at the
+           widest width -> stride-2 transposed convolutions -> head 9x9 + tanh, --norm instance | batch) through its to_inference_bf16();
+           --lr-size is the input frame, --upscale may be 1.  --fp32 then also alternates the bf16 replay and the fp32 product path as two
+           arms timed by HIP events (--ab-reps repetitions each, median and min-max); --full times one launch of each kind the pass makes on
+           the engine's own buffers, with FLOP/s and the bytes each must move per second
+
   --fp32   also times the fp32 product path (G.forward, i.e. what G.predict runs per batch) on the same weights and frames; it may run a
            smaller batch per call (--fp32-batch), stated in its line
   --full   per-layer HIP-event times of the bf16 pass (the calls the engine makes, on its buffers), with algorithmic FLOP, TFLOP/s and the
@@ -22,7 +28,8 @@ batch.  Prints one JSON line per run, shaped like ``bench.py --config c5``'s.
            output compared with the unbanded one
 
 Usage: python scripts/bench_infer_bf16.py [--lr-size 128] [--lr-width W] [--batch 32] [--kernel-size 5] [--upscale 4] [--res-blocks 16]
-                                          [--steps 10] [--warmup 3] [--fp32] [--full] [--u8] [--band-rows R] [--band-sweep R [R ...]]"""
+                                          [--steps 10] [--warmup 3] [--fp32] [--full] [--u8] [--band-rows R] [--band-sweep R [R ...]]
+                                          [--generator orig|attention|cyclegan] [--n-downsample 2] [--norm instance]"""
 import argparse
 import ctypes
 import json
@@ -69,6 +76,25 @@ def flop_frame_attention(h, w, k, f, res):
     return t + flop_conv(1, hh, ww, 128, 3, 9)
 
 
+def flop_frame_cyclegan(h, w, k, f, res, nd):
+    """make_generator_cyclegan with 64 filters: stem, nd stride-2 convolutions doubling the channels, 2 res convolutions per block at the widest
+    width, nd + log2 f transposed convolutions halving them (not below 64), head on 64"""
+    t = flop_conv(1, h, w, 3, 64, 9)
+    hh, ww, c = h, w, 64
+    for _ in range(nd):
+        hh, ww = hh // 2, ww // 2
+        t += flop_conv(1, hh, ww, c, 2 * c, k)
+        c *= 2
+    t += 2 * res * flop_conv(1, hh, ww, c, c, k)
+    ups, ff = nd, f
+    while ff > 1:
+        ups, ff = ups + 1, ff // 2
+    for _ in range(ups):
+        t += flop_convt(1, hh, ww, c, max(c // 2, 64), k)
+        hh, ww, c = 2 * hh, 2 * ww, max(c // 2, 64)
+    return t + flop_conv(1, hh, ww, 64, 3, 9)
+
+
 def time_events(fn, reps, warm=2):
     import torch
     for _ in range(warm):
@@ -96,7 +122,9 @@ def main():
     ap.add_argument("--fp32-batch", type=int, default=4)
     ap.add_argument("--full", action="store_true")
     ap.add_argument("--ab-reps", type=int, default=5)
-    ap.add_argument("--generator", choices=("orig", "attention"), default="orig")
+    ap.add_argument("--generator", choices=("orig", "attention", "cyclegan"), default="orig")
+    ap.add_argument("--n-downsample", type=int, default=2)
+    ap.add_argument("--norm", choices=("instance", "batch"), default=None)
     ap.add_argument("--u8", action="store_true")
     ap.add_argument("--u8-batches", type=int, default=4)
     ap.add_argument("--band-rows", type=int, default=None)
@@ -111,9 +139,12 @@ def main():
     h, B, k, f, res = args.lr_size, args.batch, args.kernel_size, args.upscale, args.res_blocks
     w = args.lr_width or h
     frame = "%dx%d->%dx%d" % (h, w, f * h, f * w)
-    att = args.generator == "attention"
-    make = PM.make_upscaler_attention if att else PM.make_upscaler_orig
-    G = make((f * h, f * w, 3), kernel_size=k, upscale_factor=f, res_block_num=res, seed=7)
+    att, cyc = args.generator == "attention", args.generator == "cyclegan"
+    make = PM.make_upscaler_attention if att else PM.make_generator_cyclegan if cyc else PM.make_upscaler_orig
+    kw = {} if args.norm is None and not cyc else {"norm": args.norm or "instance"}
+    if cyc:
+        kw["n_downsample"] = args.n_downsample
+    G = make((f * h, f * w, 3), kernel_size=k, upscale_factor=f, res_block_num=res, seed=7, **kw)
     inf = G.to_inference_bf16()
     rt = inf.rt
     g1 = torch.Generator().manual_seed(1234)
@@ -128,14 +159,15 @@ def main():
         inf.replay(x, br)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    fl = flop_frame_attention(h, w, k, f, res) if att else flop_frame(h, w, k, f, res)
+    fl = flop_frame_attention(h, w, k, f, res) if att else flop_frame_cyclegan(h, w, k, f, res, args.n_downsample) if cyc else flop_frame(h, w, k, f, res)
+    wl = "%s((%d,%d,3),k=%d,x%d,res=%d%s)" % (make.__name__, f * h, f * w, k, f, res, "".join(",%s=%s" % kv for kv in sorted(kw.items())))
     bf = {"metric": "upscaled frames/s (inference, generator only, bf16) at %s" % frame, "value": round(B * args.steps / dt, 2),
           "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
           "higher_is_better": True, "dtype": "bf16", "data": "synthetic",
           "gflop_per_frame": round(fl / 1e9, 1), "tflops": round(fl * B * args.steps / dt / 1e12, 1),
           "peak_share": round(fl * B * args.steps / dt / PEAK_BF16, 3),
-          "config": {"workload": "%s((%d,%d,3),k=%d,x%d,res=%d).to_inference_bf16(), BN folded, bf16 NHWC activations, "
-                                 "fp32 accumulate, batch %d, one hipGraph replay per batch" % (make.__name__, f * h, f * w, k, f, res, B),
+          "config": {"workload": "%s.to_inference_bf16(), %s, bf16 NHWC activations, "
+                                 "fp32 accumulate, batch %d, one hipGraph replay per batch" % (wl, "norm behind z" if cyc else "BN folded", B),
                      "global_batch": B, "frame": frame, "launch": "hipGraph replay", "band_rows": br,
                      "tail_bands": len(inf._plan(B, h, w, br)[1]), "tail_frames_per_launch": inf._plan(B, h, w, br)[0]}}
     print(json.dumps(bf), flush=True)
@@ -166,8 +198,11 @@ def main():
                           "config": {"workload": "G.forward(x, training=False) -- what G.predict runs per batch -- same weights and frames, "
                                                  "batch %d per call (eager launches)" % b32, "global_batch": b32, "frame": frame}}), flush=True)
 
+    if args.fp32 and cyc:
+        ab_fp32(args, G, inf, x, B, frame)
+
     if args.full:
-        (full_attention if att else full)(args, inf, x, h, w, k, f, res, B)
+        (full_attention if att else full_cyclegan if cyc else full)(args, inf, x, h, w, k, f, res, B)
 
 
 def band_sweep(args, inf, x, h, w, k, f, B):
@@ -394,6 +429,84 @@ def full_attention(args, inf, x, h, w, k, f, res, B):
     row("final/conv 9x9 %d->3 at %dx%d, %d frames per launch" % (cfin, hh, ww, ch),
         time_events(lambda: L.check(lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, Bf["y"].data_ptr(), st),
                                     "final"), args.ab_reps), flop_conv(ch, hh, ww, cfin, 3, 9))
+    for r in rows:
+        print(json.dumps(dict(r, kind="layer")), flush=True)
+
+
+def ab_fp32(args, G, inf, x, B, frame):
+    """the bf16 engine's replayed batch against the fp32 product path (G.forward(x, training=False), what G.predict runs per batch) on the same
+    weights and frames: two arms alternated after a warm-up, each repetition timed by HIP events; ms per frame, median and min-max"""
+    import statistics
+
+    import torch
+    b32 = min(args.fp32_batch, B)
+    xs = x[:b32].contiguous()
+    arms = {"bf16 engine, hipGraph replay, batch %d" % B: (lambda: inf.replay(x), B),
+            "fp32 product path, eager launches, batch %d" % b32: (lambda: G.forward(xs, training=False), b32)}
+    ms = {name: [] for name in arms}
+    with torch.no_grad():
+        for _ in range(max(5, args.ab_reps)):
+            for name, (fn, nb) in arms.items():
+                ms[name].append(time_events(fn, 3) / nb)
+    med = {name: statistics.median(v) for name, v in ms.items()}
+    names = list(arms)
+    for name, v in ms.items():
+        print(json.dumps({"kind": "bf16_vs_fp32", "arm": name, "frame": frame, "reps": len(v), "ms_per_frame_median": round(med[name], 5),
+                          "ms_per_frame_min": round(min(v), 5), "ms_per_frame_max": round(max(v), 5),
+                          "fp32_over_bf16": round(med[names[1]] / med[names[0]], 2)}), flush=True)
+
+
+def full_cyclegan(args, inf, x, h, w, k, f, res, B):
+    """one launch of each kind the cyclegan pass makes, on the engine's own buffers for its chunk of frames: HIP-event times, algorithmic FLOP
+    and TFLOP/s, and the bytes the launch must move (input read + output written, bf16; the weights are negligible) per second"""
+    import torch
+    from upscaler import _lib as L
+    rt, lib, st = inf.rt, inf.rt.lib, inf.rt.stream
+    ch = inf._chunk(B, h, w)
+    xc = x[:ch].contiguous()
+    inf.forward(x)                                    # every buffer holds a pass's data
+    torch.cuda.synchronize()
+    P = inf._launches(ch, h, w)
+    seen, rows = {}, []
+
+    def row(name, ms, flop, nbytes, count, extra=None):
+        d = {"layer": name, "launches_per_pass": count, "ms": round(ms, 4), "must_move_gb": round(nbytes / 1e9, 4),
+             "tb_per_s": round(nbytes / (ms * 1e-3) / 1e12, 3)}
+        if flop:
+            d.update({"gflop": round(flop / 1e9, 2), "tflops": round(flop / ms / 1e9, 1), "peak_share": round(flop / (ms * 1e-3) / PEAK_BF16, 4)})
+        d.update(extra or {})
+        rows.append(d)
+
+    for s in P["steps"]:
+        d, op = s["d"], s["op"]
+        key = (op["kind"], d.cin, d.h, d.w, d.cout, op["residual"], op["alpha"] is None)
+        seen.setdefault(key, []).append(s)
+    for key, steps in seen.items():
+        s = steps[0]
+        d, op = s["d"], s["op"]
+        io = (s["z"].numel() + (s["x"].numel() if s["x"] is not None else 0)) * 2 + (xc.numel() * 4 if s["x"] is None else 0)
+        fl = flop_convt(ch, d.h, d.w, d.cin, d.cout, d.kh) if op["kind"] == "convt" else flop_conv(ch, d.oh, d.ow, d.cin, d.cout, d.kh)
+        kern = {"stem": "vcg_conv9x9_from3_bf16_fwd", "convt": "vcg_conv_transpose2d_nhwc_bf16_fwd"}.get(
+            op["kind"], "vcg_conv2d_nhwc_bf16_fwd_stats (%d records per image)" % s["nrec"] if s["nrec"] > 0 else "vcg_conv2d_nhwc_bf16_fwd")
+        name = "%s %dx%d s%d %d->%d, out %dx%d, %d frames per launch" % (op["conv"], d.kh, d.kw, d.stride, d.cin, d.cout, d.oh, d.ow, ch)
+        row(name, time_events(lambda: inf._conv_step(P, s, xc), args.ab_reps), fl, io, len(steps), {"entry": kern})
+        nb = (2 + (1 if s["res"] is not None else 0)) * s["z"].numel() * 2
+        how = "norm on the moving statistics" if not inf.instance else "statistics from the epilogue records" if s["nrec"] > 0 else "statistics pass over z"
+        row("  norm%s behind it (%s): %s" % (" + PReLU" if op["alpha"] is not None else "", how, "+ Add" if s["res"] is not None else "no Add"),
+            time_events(lambda: inf._norm(P, s), args.ab_reps), 0.0, nb + (s["z"].numel() * 2 if inf.instance and s["nrec"] <= 0 else 0), len(steps))
+    wf, bf_ = inf.final
+    src = P["last"]
+    hh, ww = src.shape[1], src.shape[2]
+    df = L.ConvDesc(ch, 64, hh, ww, 3, hh, ww, 9, 9, 1, 4, 4)
+    y32 = torch.empty(ch, 3, hh, ww, device=rt.device)
+    y8 = torch.empty(ch, hh, ww, 3, dtype=torch.uint8, device=rt.device)
+    row("head/conv 9x9 64->3 + tanh at %dx%d, fp32 NCHW out, %d frames per launch (NW = 1)" % (hh, ww, ch),
+        time_events(lambda: L.check(lib.vcg_conv9x9_c64to3_bf16_fwd(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, y32.data_ptr(), st),
+                                    "head"), args.ab_reps), flop_conv(ch, hh, ww, 64, 3, 9), src.numel() * 2 + y32.numel() * 4, 1)
+    row("head/conv, window form over the whole frame, uint8 NHWC out",
+        time_events(lambda: L.check(lib.vcg_conv9x9_c64to3_bf16_fwd_window(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, L.OUT_U8_NHWC,
+                                                                           y8.data_ptr(), 0, hh, 0, hh, st), "head"), args.ab_reps),
+        flop_conv(ch, hh, ww, 64, 3, 9), src.numel() * 2 + y8.numel(), 1)
     for r in rows:
         print(json.dumps(dict(r, kind="layer")), flush=True)
 

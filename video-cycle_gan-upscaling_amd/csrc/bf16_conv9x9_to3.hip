@@ -77,7 +77,10 @@ __device__ __forceinline__ void f9_store_win(const F9WinParams& p, int img, int 
 // NW: waves per workgroup = input channels / 64 (the channel split): 4 for the 256-channel final/conv of make_upscaler_orig, 2 for the
 // 128-channel one of make_upscaler_attention (model.py:326).  A wave keeps its 64 channels, its 144 weight registers and its row slice
 // either way; a pixel is NW x 128 bytes, the workgroup NW x 64 threads and NW x 18 KiB of row buffers (so twice as many fit a CU), and
-// the NW partial rows meet in LDS as before.
+// the NW partial rows meet in LDS as before.  NW = 1 (head/conv of make_generator_cyclegan on 64 channels; descriptor form only): a
+// workgroup is one wave with 18 KiB of row buffers and two 768-byte partial rows, so eight fit a CU's LDS (2 waves per SIMD); the single
+// partial row still goes through LDS, where the wave's own lanes re-read it as 3 x 64 outputs -- the barrier has nobody else to wait
+// for, the lgkmcnt(0) in front of it is what orders the wave's stores before its loads, and a slot is rewritten two rows later.
 // OUT: F9_FULL keeps the whole-image form's code exactly.  The window forms segment [row0, row0 + rows) instead of [0, h) -- the DMA of
 // rows y0-4 .. y1+4 is the same, a row outside [0, h) still reads as zero -- and place the rows in an image of y_h rows.  F9_WIN_U8: the
 // row's 64 pixels are 192 consecutive bytes of the NHWC frame; thread t of the 192 finishes BYTE t (co = t % 3, col = t / 3, the
@@ -310,9 +313,13 @@ __global__ void pack_final9x9_kernel(const float* __restrict__ w, uint4* __restr
     out[idx] = __builtin_bit_cast(uint4, v);
 }
 
-int f9_check_desc(const vcg_conv_desc* d) {
+// c64: the entry points of head/conv on 64 channels (vcg_conv9x9_c64to3_bf16_*), which serve that channel count alone; the others keep
+// answering VCG_E_UNSUPPORTED for it
+int f9_check_desc(const vcg_conv_desc* d, bool c64 = false) {
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->oh != d->h || d->ow != d->w) return VCG_E_SHAPE;
-    if ((d->cin != 256 && d->cin != 128) || d->cout != 3 || d->kh != 9 || d->kw != 9 || d->stride != 1 || d->pad_top != 4 || d->pad_left != 4) return VCG_E_UNSUPPORTED;
+    if ((c64 ? d->cin != 64 : d->cin != 256 && d->cin != 128) || d->cout != 3 || d->kh != 9 || d->kw != 9 || d->stride != 1 || d->pad_top != 4 ||
+        d->pad_left != 4)
+        return VCG_E_UNSUPPORTED;
     return VCG_OK;
 }
 
@@ -324,7 +331,8 @@ int f9_launch(const vcg_conv_desc* d, const void* x, const void* wfrag, const vo
     const int max_grid = F9_MAX_GRID * 4 / nw;                    // half the threads and LDS per workgroup: twice the workgroups per CU
     // the descriptor form needs the image, four rows above and four below it inside 32-bit offsets
     const bool buf = ((long)d->h + 8) * d->w * (nw * 128) + 65536 <= 0xFFFFFFE0l;
-    if (out != F9_FULL && !buf) return VCG_E_UNSUPPORTED;          // (a caller bands the image so that this never happens)
+    // (a caller bands the image so that this never happens; the 64-channel layer has the descriptor form alone)
+    if ((out != F9_FULL || nw == 1) && !buf) return VCG_E_UNSUPPORTED;
     F9WinParams p;
     p.x = (const unsigned char*)x;
     p.wfrag = (const uint4*)wfrag;
@@ -357,7 +365,11 @@ int f9_launch(const vcg_conv_desc* d, const void* x, const void* wfrag, const vo
         KERNEL<<<grid, 64 * NW, lds, stream>>>(ARG);                                                                        \
     } while (0)
     const F9Params& whole = p;
-    if (out == F9_WIN_F32) {
+    if (nw == 1) {               // one wave per workgroup: 2048 workgroups of 19.5 KiB of LDS, eight per CU
+        if (out == F9_WIN_F32) VCG_F9_LAUNCH((conv9x9_c256to3_bf16_kernel<true, 1, F9_WIN_F32, F9WinParams>), 1, p);
+        else if (out == F9_WIN_U8) VCG_F9_LAUNCH((conv9x9_c256to3_bf16_kernel<true, 1, F9_WIN_U8, F9WinParams>), 1, p);
+        else VCG_F9_LAUNCH((conv9x9_c256to3_bf16_kernel<true, 1>), 1, whole);
+    } else if (out == F9_WIN_F32) {
         if (nw == 4) VCG_F9_LAUNCH((conv9x9_c256to3_bf16_kernel<true, 4, F9_WIN_F32, F9WinParams>), 4, p);
         else VCG_F9_LAUNCH((conv9x9_c256to3_bf16_kernel<true, 2, F9_WIN_F32, F9WinParams>), 2, p);
     } else if (out == F9_WIN_U8) {
@@ -419,6 +431,40 @@ int vcg_conv9x9_to3_bf16_fwd_window(const vcg_conv_desc* d, const void* x, const
     if (int e = f9_check_desc(d)) return e;
     if (rows <= 0 || row0 < 0 || (long)row0 + rows > d->h || y_row0 < 0 || (long)y_row0 + rows > y_h) return VCG_E_SHAPE;
     if (int e = f9_check_desc(d)) return e;
+    if (out_kind != VCG_OUT_F32_NCHW && out_kind != VCG_OUT_U8_NHWC) return VCG_E_UNSUPPORTED;
+    return f9_launch(d, x, wfrag, bias, tanh_act, y, out_kind == VCG_OUT_U8_NHWC ? F9_WIN_U8 : F9_WIN_F32, row0, rows, y_row0, y_h, stream);
+}
+
+// head/conv of make_generator_cyclegan: the same layer on 64 input channels, one wave per workgroup (NW = 1)
+size_t vcg_conv9x9_c64to3_bf16_wfrag_bytes(void) { return (size_t)(F_NFRAG / 4 + 4) * 16; }
+
+int vcg_pack_conv9x9_c64to3_bf16(const void* w, void* out, hipStream_t stream) {
+    VCG_CHECK_PTR(w);
+    VCG_CHECK_PTR(out);
+    const int total = F_NFRAG / 4 + 4;
+    pack_final9x9_kernel<<<(total + 255) / 256, 256, 0, stream>>>((const float*)w, (uint4*)out, 64);
+    VCG_LAUNCH_CHECK();
+    return VCG_OK;
+}
+
+int vcg_conv9x9_c64to3_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* wfrag, const void* bias, int32_t tanh_act, void* y,
+                                hipStream_t stream) {
+    VCG_CHECK_PTR(d);
+    VCG_CHECK_PTR(x);
+    VCG_CHECK_PTR(wfrag);
+    VCG_CHECK_PTR(y);
+    if (int e = f9_check_desc(d, true)) return e;
+    return f9_launch(d, x, wfrag, bias, tanh_act, y, F9_FULL, 0, d->h, 0, d->h, stream);
+}
+
+int vcg_conv9x9_c64to3_bf16_fwd_window(const vcg_conv_desc* d, const void* x, const void* wfrag, const void* bias, int32_t tanh_act,
+                                       int32_t out_kind, void* y, int32_t row0, int32_t rows, int32_t y_row0, int32_t y_h, hipStream_t stream) {
+    VCG_CHECK_PTR(d);
+    VCG_CHECK_PTR(x);
+    VCG_CHECK_PTR(wfrag);
+    VCG_CHECK_PTR(y);
+    if (int e = f9_check_desc(d, true)) return e;
+    if (rows <= 0 || row0 < 0 || (long)row0 + rows > d->h || y_row0 < 0 || (long)y_row0 + rows > y_h) return VCG_E_SHAPE;
     if (out_kind != VCG_OUT_F32_NCHW && out_kind != VCG_OUT_U8_NHWC) return VCG_E_UNSUPPORTED;
     return f9_launch(d, x, wfrag, bias, tanh_act, y, out_kind == VCG_OUT_U8_NHWC ? F9_WIN_U8 : F9_WIN_F32, row0, rows, y_row0, y_h, stream);
 }

@@ -670,6 +670,13 @@ def pack_conv9x9_to3_bf16(rt, w, cin, out=None):
     return out
 
 
+def pack_conv9x9_c64to3_bf16(rt, w, out=None):
+    """Conv2D (9,9,64,3) for vcg_conv9x9_c64to3_bf16_fwd[_window]"""
+    out = _bytes(rt, rt.lib.vcg_conv9x9_c64to3_bf16_wfrag_bytes()) if out is None else out
+    L.check(rt.lib.vcg_pack_conv9x9_c64to3_bf16(w.data_ptr(), out.data_ptr(), rt.stream), "vcg_pack_conv9x9_c64to3_bf16")
+    return out
+
+
 def pack_conv_kernel_bf16(rt, w, taps, a, b, transpose, flip, out=None):
     """[tap][a][b] bf16 (include/vcg.h: vcg_pack_conv_kernel_bf16), what the 3x3 64-channel kernels read"""
     out = _bf16(rt, taps, a, b) if out is None else out

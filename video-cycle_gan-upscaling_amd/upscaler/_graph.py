@@ -598,4 +598,15 @@ def make_generator_cyclegan(output_image_shape, filters=64, n_downsample=2, res_
         model = conv2d_transpose(model, ch, kernel_size, 2, name="up/%d/conv_transp" % i)
         model = batch_norm_prelu(model, name="up/%d/norm" % i, prelu_name="up/%d/prelu" % i, norm=norm)
     model = conv2d(model, 3, 9, 1, "same", activation="tanh", name="head/conv")
-    return build_model(inp, model, name="generator_cyclegan", seed=seed)
+    net = build_model(inp, model, name="generator_cyclegan", seed=seed)
+    # what the bf16 inference engine recognises the topology by (not the name string), and its entry point
+    net.cyclegan_generator = {"filters": filters, "n_downsample": n_downsample, "res_block_num": res_block_num, "upscale_factor": f, "norm": norm,
+                              "kernel_size": kernel_size, "channels": output_image_shape[2]}
+    net.to_inference_bf16 = lambda: _cyclegan_bf16(net)
+    return net
+
+
+def _cyclegan_bf16(net):
+    """inference engine on the bf16-storage kernels (one hipGraph per input shape): ``_infer.Bf16CycleGanGenerator``"""
+    from ._infer import Bf16CycleGanGenerator
+    return Bf16CycleGanGenerator(net)

@@ -249,6 +249,11 @@ class Bf16Generator:
                                "us": [flat(ch * 4 ** (s + 1) * rows * w * 256) for s in range(len(self.ups))], "y": y}
         return self._bufs[key]
 
+    def _factor(self):
+        """output frame size / input frame size: one doubling per up-sampling stage here and in the attention generator; an engine whose
+        up-sampling stages also undo down-sampling ones (Bf16CycleGanGenerator) overrides it"""
+        return 2 ** len(self.ups)
+
     def _tail_chunk(self, n, h, w):
         """frames per launch of the up-sampling stages and final/conv of an unbanded tail.  Beyond the k3 x2 topology, a launch's largest
         tensor (the last stage's output, 2 * 256 bytes per pixel) stays below 4 GiB: the kernels' offsets are 32-bit inside an image, and
@@ -420,7 +425,7 @@ class Bf16Generator:
         if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3:
             raise ValueError("expected uint8 frames [N,h,w,3], got %s %s" % (t.dtype, tuple(t.shape)))
         n, h, w, _ = t.shape
-        f = 2 ** len(self.ups)
+        f = self._factor()
         out = np.empty((n, f * h, f * w, 3), dtype=np.uint8)
         if n == 0:
             return out
@@ -647,4 +652,257 @@ class Bf16AttentionGenerator(Bf16Generator):
             else:
                 L.check(rt.lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, y[i:i + c].data_ptr(),
                                                         rt.stream), "vcg_conv9x9_to3_bf16_fwd")
+        return y
+
+
+class Bf16CycleGanGenerator(Bf16Generator):
+    """The same engine for ``make_generator_cyclegan`` models (_graph.py; BASELINE.json north_star's generator shape, SURVEY.md section 8
+    row a11), filters 64 on RGB frames, norm 'instance' or 'batch', kernel_size 3 or 5, n_downsample 1 or 2, upscale_factor 1, 2 or 4, any
+    res_block_num:
+
+        stem/conv 9x9 3->64 + bias                              vcg_conv9x9_from3_bf16_fwd without activation -> z
+        down/i/conv k s2 (64 -> 128 -> 256) + bias              vcg_conv2d_nhwc_bf16_fwd[_stats] -> z
+        res_block/i/conv_pre | conv_post k s1 + bias            the same
+        up/i/conv_transp k s2 (halving, not below 64) + bias    vcg_conv_transpose2d_nhwc_bf16_fwd -> z
+        the norm + PReLU (+ Add of the block input) behind every one of them: vcg_norm_act_fwd_bf16 on z, with
+            instance norm: per-image scale / shift from the convolution's epilogue records (vcg_norm_finalize_partials) where its tiled
+                           kernel serves the shape, otherwise from vcg_norm_stats_bf16 + vcg_norm_finalize -- the statistics of the
+                           stored bf16 z either way;
+            batch norm:    per-channel scale / shift of the moving statistics (vcg_bn_fold without bias: the bias is in z), made in refresh()
+        head/conv 9x9 64->3 + tanh                              vcg_conv9x9_c64to3_bf16_fwd, or its window form over the whole frame for
+                                                                uint8 frames
+
+    Activations are bf16 NHWC, the weights are rounded to bf16 once in refresh(); biases, norm and PReLU parameters stay fp32.
+    capture / replay / predict / upscale_frames are Bf16Generator's.  The generic kernels address the whole batch of a launch with 32-bit
+    offsets, so the pass runs on chunks of frames whose largest tensor fits LAUNCH_LIMIT bytes, spread evenly (instance statistics are
+    per image and inference BatchNormalization per pixel: chunking changes no value).  No row bands."""
+    LAUNCH_LIMIT = TAIL_LIMIT          # bytes of a launch's largest tensor; a class attribute so that a test can lower it
+    SERVED = "bf16 inference of make_generator_cyclegan is instantiated for filters=64 on 3-channel (RGB) frames, norm 'instance' or " \
+             "'batch', kernel_size 3 or 5, n_downsample 1 or 2 and upscale_factor 1, 2 or 4 (any res_block_num); use model.predict for " \
+             "other shapes"
+    SERVED_SIZE = "bf16 inference of make_generator_cyclegan runs on whole frames (band_rows=None) whose largest tensor, f*h x f*w x 64 " \
+                  "channels in bf16, fits a launch of 4 GiB; row bands are served for make_upscaler_orig models only"
+
+    def __init__(self, model):
+        cfg = getattr(model, "cyclegan_generator", None)
+        if cfg is None or not hasattr(model, "graph"):
+            raise TypeError("Bf16CycleGanGenerator serves make_generator_cyclegan models")
+        if cfg["filters"] != 64 or cfg["channels"] != 3 or cfg["norm"] not in ("instance", "batch") or cfg["kernel_size"] not in (3, 5) \
+                or cfg["n_downsample"] not in (1, 2) or cfg["upscale_factor"] not in (1, 2, 4):
+            raise NotImplementedError(self.SERVED)
+        self.k, self.n_downsample, self.res_block_num = cfg["kernel_size"], cfg["n_downsample"], cfg["res_block_num"]
+        self.upscale_factor = cfg["upscale_factor"]
+        self.legacy = False
+        self.instance = cfg["norm"] == "instance"
+        self.model = model
+        self.rt = model.rt
+        self.layers = {l.name: l for l in model.layers}
+        self._graphs = {}
+        self._bufs = {}
+        self.refresh()
+
+    def _factor(self):
+        return self.upscale_factor
+
+    # ---- parameters ------------------------------------------------------------------------------------------
+    def _op(self, kind, conv, norm, out, residual=False):
+        """one convolution and the norm (+ PReLU, + Add) behind it.  kind: 'stem' | 'conv' | 'convt'; out: the name of the stored result"""
+        rt, ps, ly = self.rt, self.model.ps, self.layers
+        cv, nm = ly[conv], ly[norm]
+        if kind == "stem":
+            w = E.pack_first9x9_bf16(rt, ps[conv + "/kernel"])
+        else:               # the generic kernels' fragments: mode 0 for a Conv2D, mode 1 for a Conv2DTranspose (_pack)
+            w = E.pack_conv_frag_bf16(rt, ps[conv + "/kernel"], cv.k * cv.k, cv.cout, cv.cin, 1 if kind == "convt" else 0)
+        scale = shift = None
+        if not self.instance:
+            scale, shift = rt.empty(cv.cout), rt.empty(cv.cout)
+            L.check(rt.lib.vcg_bn_fold(None, ps[norm + "/moving_mean"].data_ptr(), ps[norm + "/moving_variance"].data_ptr(),
+                                       ps[norm + "/gamma"].data_ptr(), ps[norm + "/beta"].data_ptr(), cv.cout, E.BN_EPS, scale.data_ptr(),
+                                       shift.data_ptr(), rt.stream), "vcg_bn_fold")
+        alpha = ps[nm.prelu_name + "/alpha"] if nm.act == L.ACT_PRELU else None
+        return {"kind": kind, "conv": conv, "layer": cv, "w": w, "bias": ps[conv + "/bias"], "scale": scale, "shift": shift, "alpha": alpha,
+                "out": out, "residual": residual}
+
+    def refresh(self):
+        """(re)derive the packed bf16 weights and the BatchNormalization scale / shift vectors from the model's parameters"""
+        ops = [self._op("stem", "stem/conv", "stem/norm", "stem/prelu")]
+        for i in range(self.n_downsample):
+            ops.append(self._op("conv", "down/%d/conv" % i, "down/%d/norm" % i, "down/%d/prelu" % i))
+        for i in range(self.res_block_num):
+            n = "res_block/%d" % i
+            ops.append(self._op("conv", n + "/conv_pre", n + "/batch_norm_pre", n + "/prelu"))
+            ops.append(self._op("conv", n + "/conv_post", n + "/batch_norm_post", n + "/final_add", residual=True))
+        self.ups = []
+        for i in range(self.n_downsample + {1: 0, 2: 1, 4: 2}[self.upscale_factor]):
+            self.ups.append(self._op("convt", "up/%d/conv_transp" % i, "up/%d/norm" % i, "up/%d/prelu" % i))
+        self.ops = ops + self.ups
+        ps = self.model.ps
+        self.final = (E.pack_conv9x9_c64to3_bf16(self.rt, ps["head/conv/kernel"]), ps["head/conv/bias"])
+        self._graphs.clear()          # recorded graphs hold the old parameter buffers
+        self._bufs.clear()            # (the plans name the operands of the ops above)
+        self._staging = None          # upscale_frames' pinned and device staging buffers
+
+    # ---- launch plan -----------------------------------------------------------------------------------------
+    def _shapes(self, h, w):
+        """[(cin, ih, iw, cout, oh, ow)] of self.ops for h x w frames"""
+        if h % (1 << self.n_downsample) or w % (1 << self.n_downsample):
+            raise ValueError("frames of %d x %d are not divisible by 2**n_downsample" % (h, w))
+        out, c = [], 3
+        for op in self.ops:
+            cv = op["layer"]
+            oh, ow = (2 * h, 2 * w) if op["kind"] == "convt" else cv.out_hw(h, w)[:2]
+            out.append((c, h, w, cv.cout, oh, ow))
+            c, h, w = cv.cout, oh, ow
+        return out
+
+    def _chunk(self, n, h, w):
+        """frames per launch: as many as keep every tensor of the pass within LAUNCH_LIMIT bytes, spread evenly over the launches"""
+        shapes = self._shapes(h, w)
+        f = self._factor()
+        per = max(max(ci * ih * iw, co * oh * ow) for (ci, ih, iw, co, oh, ow) in shapes[1:]) * 2
+        per = max(per, shapes[0][3] * h * w * 2)
+        # head/conv's descriptor covers one image, four rows above and four below it
+        if per > self.LAUNCH_LIMIT or (f * h + 8) * f * w * 128 + 65536 > self.LAUNCH_LIMIT:
+            raise NotImplementedError(self.SERVED_SIZE)
+        ch = max(1, min(n, self.LAUNCH_LIMIT // per))
+        launches = -(-n // ch)
+        return -(-n // launches)
+
+    def _plan(self, n, h, w, band_rows=None, out_kind=L.OUT_F32_NCHW):
+        if band_rows is not None:
+            raise NotImplementedError(self.SERVED_SIZE)
+        return self._chunk(n, h, w), ()
+
+    def _launches(self, c, h, w):
+        """the pass for c frames of h x w pixels: per op its descriptor, buffers and -- decided here, once per layer shape -- whether the
+        instance statistics come out of the convolution's epilogue (records > 0) or from a pass over z"""
+        key = ("pass", c, h, w)
+        if key in self._bufs:
+            return self._bufs[key]
+        rt, dev, pool = self.rt, self.rt.device, {}
+
+        def buf(role, hh, ww, cc):
+            if (role, hh, ww, cc) not in pool:
+                pool[(role, hh, ww, cc)] = torch.empty(c, hh, ww, cc, dtype=torch.bfloat16, device=dev)
+            return pool[(role, hh, ww, cc)]
+
+        steps, cur, block_in, crop, maxrec = [], None, None, max(self.k - 2, 0) // 2, 0
+        for op, (ci, ih, iw, co, oh, ow) in zip(self.ops, self._shapes(h, w)):
+            cv, nrec = op["layer"], -1
+            if op["kind"] == "stem":
+                d = L.ConvDesc(c, 3, ih, iw, co, oh, ow, 9, 9, 1, 4, 4)
+            elif op["kind"] == "convt":          # TF-SAME crop of Conv2DTranspose(k, strides 2): k3 (0, 1), k5 (1, 2)
+                d = L.ConvDesc(c, ci, ih, iw, co, oh, ow, self.k, self.k, 2, crop, crop)
+            else:
+                d = cv.desc(c, ih, iw)
+                if self.instance:
+                    nrec = rt.lib.vcg_conv2d_nhwc_bf16_stats_records(ctypes.byref(d), L.STATS_INSTANCE)
+                    maxrec = max(maxrec, nrec * co)
+            if op["conv"].endswith("/conv_pre"):
+                block_in = cur
+            # outputs: a residual block's PReLU in "b", its sum in whichever of "a" / "c" does not hold the block input; everything else
+            # in "a" of its own shape (two consecutive layers outside the trunk never share one)
+            role = "b" if op["conv"].endswith("/conv_pre") else "a"
+            if op["residual"] and block_in is buf("a", oh, ow, co):
+                role = "c"
+            y = buf(role, oh, ow, co)
+            steps.append({"op": op, "d": d, "x": cur, "z": buf("z", oh, ow, co), "y": y, "nrec": nrec, "c": co, "hw": oh * ow,
+                          "res": block_in if op["residual"] else None})
+            cur = y
+        P = {"steps": steps, "last": cur,
+             "stats": torch.empty(5, c * 256, dtype=torch.float32, device=dev) if self.instance else None,
+             "part": torch.empty(max(1, c * maxrec * 2), dtype=torch.float32, device=dev) if self.instance else None}
+        self._bufs[key] = P
+        return P
+
+    def stats_records(self, n, h, w):
+        """{convolution name: records per image of its epilogue statistics, or a negative number where a separate pass over z makes them}
+        for the instance-norm layers of one launch of n frames (what the tests assert the covered paths with)"""
+        return {s["op"]["conv"]: s["nrec"] for s in self._launches(n, h, w)["steps"] if s["op"]["kind"] == "conv"}
+
+    # ---- one forward pass --------------------------------------------------------------------------------------
+    def _norm(self, P, s):
+        """the norm (+ PReLU, + Add) behind a convolution: z -> y"""
+        rt, op, c = self.rt, s["op"], s["z"].shape[0]
+        z, co, hw = s["z"], s["c"], s["hw"]
+        if self.instance:
+            mean, var, scale, shift, invstd = (P["stats"][i] for i in range(5))
+            if s["nrec"] > 0:
+                L.check(rt.lib.vcg_norm_finalize_partials(P["part"].data_ptr(), s["nrec"], c, co, float(hw), None, None, E.IN_EPS,
+                                                          mean.data_ptr(), scale.data_ptr(), shift.data_ptr(), invstd.data_ptr(), None, None,
+                                                          0.0, 0, rt.stream), "vcg_norm_finalize_partials")
+            else:
+                ws, wsn = rt.workspace(rt.lib.vcg_norm_stats_bf16_workspace_bytes(c, co, hw, L.NORM_INSTANCE))
+                L.check(rt.lib.vcg_norm_stats_bf16(z.data_ptr(), c, co, hw, L.NORM_INSTANCE, mean.data_ptr(), var.data_ptr(), ws, wsn,
+                                                   rt.stream), "vcg_norm_stats_bf16")
+                L.check(rt.lib.vcg_norm_finalize(mean.data_ptr(), var.data_ptr(), None, None, co, c, E.IN_EPS, scale.data_ptr(),
+                                                 shift.data_ptr(), invstd.data_ptr(), None, None, 0.0, 0, rt.stream), "vcg_norm_finalize")
+            per_sample = 1
+        else:
+            scale, shift, per_sample = op["scale"], op["shift"], 0
+        alpha = op["alpha"]
+        L.check(rt.lib.vcg_norm_act_fwd_bf16(z.data_ptr(), c, co, hw, scale.data_ptr(), shift.data_ptr(), per_sample,
+                                             L.ACT_PRELU if alpha is not None else L.ACT_NONE, 0.0,
+                                             alpha.data_ptr() if alpha is not None else None,
+                                             s["res"].data_ptr() if s["res"] is not None else None, s["y"].data_ptr(), rt.stream),
+                "vcg_norm_act_fwd_bf16")
+
+    def _conv_step(self, P, s, x):
+        """the convolution (+ bias) of one step: its input (the frames x for the stem) -> z, with the statistics records where planned"""
+        rt = self.rt
+        op, d, z = s["op"], s["d"], s["z"]
+        if op["kind"] == "stem":
+            L.check(rt.lib.vcg_conv9x9_from3_bf16_fwd(ctypes.byref(d), x.data_ptr(), op["w"].data_ptr(), op["bias"].data_ptr(), None,
+                                                      z.data_ptr(), rt.stream), "vcg_conv9x9_from3_bf16_fwd")
+        elif op["kind"] == "convt":
+            L.check(rt.lib.vcg_conv_transpose2d_nhwc_bf16_fwd(ctypes.byref(d), s["x"].data_ptr(), op["w"].data_ptr(), op["bias"].data_ptr(),
+                                                              L.ACT_NONE, 0.0, z.data_ptr(), rt.stream), "vcg_conv_transpose2d_nhwc_bf16_fwd")
+        elif s["nrec"] > 0:
+            L.check(rt.lib.vcg_conv2d_nhwc_bf16_fwd_stats(ctypes.byref(d), s["x"].data_ptr(), op["w"].data_ptr(), op["bias"].data_ptr(),
+                                                          z.data_ptr(), P["part"].data_ptr(), rt.stream), "vcg_conv2d_nhwc_bf16_fwd_stats")
+        else:
+            L.check(rt.lib.vcg_conv2d_nhwc_bf16_fwd(ctypes.byref(d), s["x"].data_ptr(), op["w"].data_ptr(), op["bias"].data_ptr(),
+                                                    L.ACT_NONE, 0.0, z.data_ptr(), rt.stream), "vcg_conv2d_nhwc_bf16_fwd")
+
+    def _pass(self, x, y, out_kind, taps):
+        """the pass on one chunk: x fp32 NCHW [c,3,h,w] -> y (its frames of the output buffer)"""
+        rt = self.rt
+        c, _, h, w = x.shape
+        P = self._launches(c, h, w)
+
+        def tap(name, t):
+            if taps is not None:
+                taps[name] = torch.cat([taps[name], t.clone()], 0) if name in taps else t.clone()
+
+        for s in P["steps"]:
+            self._conv_step(P, s, x)
+            tap(s["op"]["conv"], s["z"])
+            self._norm(P, s)
+            tap(s["op"]["out"], s["y"])
+        wf, bf_ = self.final
+        f = self._factor()
+        df = L.ConvDesc(c, 64, f * h, f * w, 3, f * h, f * w, 9, 9, 1, 4, 4)
+        if out_kind == L.OUT_U8_NHWC:             # the whole frame as one window: head/conv stores the uint8 NHWC frames
+            L.check(rt.lib.vcg_conv9x9_c64to3_bf16_fwd_window(ctypes.byref(df), P["last"].data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, out_kind,
+                                                              y.data_ptr(), 0, f * h, 0, f * h, rt.stream), "vcg_conv9x9_c64to3_bf16_fwd_window")
+        else:
+            L.check(rt.lib.vcg_conv9x9_c64to3_bf16_fwd(ctypes.byref(df), P["last"].data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, y.data_ptr(),
+                                                       rt.stream), "vcg_conv9x9_c64to3_bf16_fwd")
+        tap("head/conv", y)
+
+    def forward(self, x, out_kind=L.OUT_F32_NCHW, band_rows=None, taps=None):
+        """x: device fp32 NCHW [n,3,h,w] in [-1,1] -> device fp32 NCHW [n,3,f*h,f*w], or with out_kind OUT_U8_NHWC device uint8 frames
+        [n,f*h,f*w,3] (f = upscale_factor; buffer owned by the engine).  taps: a dict that receives a clone of every tensor the pass
+        stores, keyed by layer name ("stem/conv", "stem/prelu", ..., "res_block/0/final_add", ..., "head/conv"): a debugging hook for
+        eager calls, never used inside a capture"""
+        n, _, h, w = x.shape
+        ch, _ = self._plan(n, h, w, band_rows, out_kind)
+        f = self._factor()
+        key = ("y", n, h, w, out_kind)
+        if key not in self._bufs:
+            self._bufs[key] = (torch.empty(n, f * h, f * w, 3, dtype=torch.uint8, device=self.rt.device) if out_kind == L.OUT_U8_NHWC
+                               else torch.empty(n, 3, f * h, f * w, dtype=torch.float32, device=self.rt.device))
+        y = self._bufs[key]
+        for i in range(0, n, ch):
+            self._pass(x[i:i + ch], y[i:i + ch], out_kind, taps)
         return y

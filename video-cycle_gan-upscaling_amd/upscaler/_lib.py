@@ -150,6 +150,10 @@ SIGNATURES = {
     "vcg_conv9x9_to3_bf16_fwd_window": (c_int, [_D, _P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P]),
     "vcg_conv9x9_to3_bf16_wfrag_bytes": (c_size_t, [c_int]),
     "vcg_pack_conv9x9_to3_bf16": (c_int, [_P, c_int, _P, _P]),
+    "vcg_conv9x9_c64to3_bf16_wfrag_bytes": (c_size_t, []),
+    "vcg_pack_conv9x9_c64to3_bf16": (c_int, [_P, _P, _P]),
+    "vcg_conv9x9_c64to3_bf16_fwd": (c_int, [_D, _P, _P, _P, c_int, _P, _P]),
+    "vcg_conv9x9_c64to3_bf16_fwd_window": (c_int, [_D, _P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P]),
     "vcg_conv_in_gate_bf16_wfrag_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "vcg_pack_conv_in_gate_bf16": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "vcg_conv_in_gate_bf16_fwd": (c_int, [_D, _P, _P, _P, _P, _P, _P]),
