@@ -333,8 +333,9 @@ int vcg_conv9x9_to3_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* 
 /* the same layer on 128 or 256 input channels: d->cin = 128 is final/conv of make_upscaler_attention (upscaling/upscaler/model.py:326, after
  * up-sampling blocks of 128 filters).  vcg_conv9x9_to3_bf16_fwd accepts both; wfrag is then vcg_conv9x9_to3_bf16_wfrag_bytes(cin) bytes
  * (cin/64 * 2304 fragments of 16 bytes + 64 zero bytes; 0 for an unsupported cin) made by vcg_pack_conv9x9_to3_bf16 from Keras' (9,9,cin,3)
- * fp32 kernel.  At cin = 256 size and contents equal VCG_FINAL9X9_WFRAG_BYTES / vcg_pack_final9x9_bf16.  The gradients of this layer
- * (vcg_conv9x9_to3_bf16_dgrad*) stay 256-only. */
+ * fp32 kernel.  At cin = 256 size and contents equal VCG_FINAL9X9_WFRAG_BYTES / vcg_pack_final9x9_bf16.  The gradients of this layer:
+ * vcg_conv9x9_to3_bf16_dgrad* take any cin = 64 * {1,2,4,8} (their kernel is the 3 -> cin forward kernel on
+ * vcg_pack_conv9x9_3ch_bf16(w, cin, 1); cin = 64 is head/conv of make_generator_cyclegan), vcg_conv9x9_to3_bf16_wgrad 64 and 256. */
 size_t vcg_conv9x9_to3_bf16_wfrag_bytes(int32_t cin);
 int vcg_pack_conv9x9_to3_bf16(const void* w, int32_t cin, void* out, hipStream_t stream);
 /* final/conv over a window of rows: what lets an inference engine run the tail on row bands of a frame and write uint8 frames directly.
@@ -374,7 +375,7 @@ int vcg_pack_first9x9_bf16(const void* w, void* out, hipStream_t stream);
  * cout -> 3 convolution (final/conv, model.py:290), packed for its data gradient (taps flipped, roles of in/out swapped) */
 int vcg_pack_conv9x9_3ch_bf16(const void* w, int32_t cout, int32_t dgrad, void* out, hipStream_t stream);
 /* data gradient of final/conv on the bf16 path: dy fp32 NCHW [n,3,h,w] -> dx bf16 NHWC [n,h,w,cin]; d describes the FORWARD
- * convolution (cin = 256, cout = 3).  y_prev (optional): the bf16 NHWC output of the LeakyReLU feeding the convolution
+ * convolution (cin = 256, or another 64 * {1,2,4,8}; cout = 3).  y_prev (optional): the bf16 NHWC output of the LeakyReLU feeding the convolution
  * (upsampling_block, model.py:73); dx is then multiplied by its derivative, i.e. it is the gradient in front of the activation. */
 int vcg_conv9x9_to3_bf16_dgrad(const vcg_conv_desc* d, const void* dy, const void* wfrag, const void* y_prev, float lrelu_slope, void* dx,
                                hipStream_t stream);
@@ -478,7 +479,12 @@ int vcg_conv2d_bf16_wgrad(const vcg_conv_desc* d, const void* x, const void* dy,
 
 /* weight gradient of final/conv -- Conv2D(3, 9, 'same') on 256 channels (upscaling/upscaler/model.py:290) -- in the bf16 configs:
  * x bf16 NHWC [n][h][w][256], dz fp32 NCHW [n][3][h][w] (the gradient behind the tanh; rounded to bf16 as an MFMA operand), dw fp32 in
- * Keras' (9,9,256,3) layout, overwritten.  w must be even.  (The bias gradient is the channel sum of dz: vcg_act_bwd / vcg_channel_sum.) */
+ * Keras' (9,9,256,3) layout, overwritten.  w must be even.  (The bias gradient is the channel sum of dz: vcg_act_bwd / vcg_channel_sum.)
+ * d->cin = 64 is head/conv of make_generator_cyclegan (the same model.py:290 layer behind a 64-channel up-sampling stage): x
+ * [n][h][w][64], dw (9,9,64,3), a kernel of its own (128-byte pixels, two row tiles per wave); deterministic like the 256 form: a second
+ * call is bit-identical.  Replaces the gradient Keras derives for model.py:290.  Other channel counts: the query returns 0 and the call
+ * VCG_E_UNSUPPORTED; an odd width: VCG_E_UNSUPPORTED (run vcg_conv2d_wgrad on an fp32 copy of x); a workspace below the query:
+ * VCG_E_WORKSPACE. */
 size_t vcg_conv9x9_to3_bf16_wgrad_workspace_bytes(const vcg_conv_desc* d);
 int vcg_conv9x9_to3_bf16_wgrad(const vcg_conv_desc* d, const void* x, const float* dz, float* dw_hwio, void* ws, size_t ws_bytes, hipStream_t stream);
 
@@ -516,6 +522,15 @@ int vcg_conv_transpose2d_nhwc_bf16_fwd(const vcg_conv_desc* d, const void* x, co
  * OUTPUT mask_src is and which feeds the layer. */
 int vcg_conv2d_nhwc_bf16_dgrad(const vcg_conv_desc* d, const void* dy, const void* wfrag_t, const void* mask_src, float mask_slope,
                                void* dx, hipStream_t stream);
+/* dx = bf16(data gradient + dx_residual): the data gradient of a 3x3 stride-1 'same' convolution whose input also feeds a skip branch --
+ * conv_pre of residual_block (upscaling/upscaler/model.py:19, the Add of :26 hands its gradient to the block input unchanged) -- with that
+ * second gradient dx_residual (bf16 NHWC of dx's shape) added in fp32 before the one rounding to bf16.  Replaces the gradient sum Keras
+ * derives for the tensor read by model.py:19 and :26.  d is the FORWARD layer, wfrag_t packed with mode 1; cin and cout multiples of 64.
+ * With an all-zero dx_residual the result equals vcg_conv2d_nhwc_bf16_dgrad bit for bit.  No workspace.  VCG_E_NULL: any pointer NULL;
+ * VCG_E_SHAPE: oh/ow differ from h/w; VCG_E_UNSUPPORTED: stride != 1, a kernel other than 3x3 with pads 1, channel counts that are no
+ * multiple of 64, dx_residual == dx (the operands must not overlap). */
+int vcg_conv2d_nhwc_bf16_dgrad_add(const vcg_conv_desc* d, const void* dy, const void* wfrag_t, const void* dx_residual, void* dx,
+                                   hipStream_t stream);
 /* weight / bias gradient, x [n][h][w][cin] and dy [n][oh][ow][cout] bf16 NHWC, 3x3 / 4x4 / 5x5, stride 1 / 2, channels multiples of 64;
  * dw fp32 in Keras' (kh,kw,in,out) layout, dbias fp32 [cout] or NULL (deterministic: fixed-order sum of per-workgroup partials).
  * 5x5 (the trunk of kernel_size=5 generators, model.py:267): the 25 taps are split over two workgroups per (ci, co) block pair, so the

@@ -589,7 +589,8 @@ bool plan_gconv_lds(const GcParams& p, GlParams& q, int& spe_out, bool& half_out
     q.osy = p.osy; q.osx = p.osx; q.ooy = p.ooy; q.oox = p.oox; q.mblocks = p.mblocks; q.act = p.act; q.alpha = p.alpha; q.mask_slope = p.mask_slope;
     q.isy = p.isy; q.isx = p.isx; q.stats = p.stats;
     q.tiles_x = ceil_div(p.low, GL_TC); q.tiles_y = ceil_div(p.loh, GL_TR);
-    half_out = p.mblocks == 2 && p.stats == nullptr && spe <= 3;     // 64 output channels: waves = 2 channel blocks x 2 row halves (+ loaders, three stages)
+    // 64 output channels: waves = 2 channel blocks x 2 row halves (+ loaders, three stages); the epilogue terms are instantiated in the one-role form only
+    half_out = p.mblocks == 2 && p.stats == nullptr && spe <= 3 && !(p.scale || p.prelu || p.res);
     q.mgroups = half_out ? 1 : (p.mblocks + 3) / 4;
     const long pairs = (long)p.n * q.tiles_x * q.tiles_y * q.mgroups;
     if ((check_pairs && pairs < 64) || pairs > 0x7fffffffL) return false;        // too little work for 256 one-workgroup CUs: the streaming kernel's small tiles fill the chip better
@@ -602,8 +603,10 @@ bool plan_gconv_lds(const GcParams& p, GlParams& q, int& spe_out, bool& half_out
 
 int launch_gconv_lds(const GlParams& q, int spe, bool half, hipStream_t st) {
     const int grid = q.pairs < 256 ? q.pairs : 256;
-    if (q.scale || q.prelu || q.res)                           // the epilogue terms: instantiated for the 5x5 trunk convolution's plan only
-        return spe == 4 && !half ? launch_gconv_lds_sp<4, false, true>(q, grid, st) : VCG_E_UNSUPPORTED;
+    if (q.scale || q.prelu || q.res) {                         // the epilogue terms: the 5x5 trunk convolution's plan and the 3x3 data gradient with a joining gradient
+        if (half) return VCG_E_UNSUPPORTED;
+        return spe == 4 ? launch_gconv_lds_sp<4, false, true>(q, grid, st) : spe == 2 ? launch_gconv_lds_sp<2, false, true>(q, grid, st) : VCG_E_UNSUPPORTED;
+    }
     switch (spe) {
         case 1: return half ? launch_gconv_lds_sp<1, true>(q, grid, st) : launch_gconv_lds_sp<1, false>(q, grid, st);
         case 2: return half ? launch_gconv_lds_sp<2, true>(q, grid, st) : launch_gconv_lds_sp<2, false>(q, grid, st);
@@ -884,6 +887,31 @@ int vcg_conv2d_nhwc_bf16_dgrad(const vcg_conv_desc* d, const void* dy, const voi
         if (rc) return rc;
     }
     return VCG_OK;
+}
+
+// dx = bf16(data gradient + dx_residual) of a stride-1 3x3 'same' convolution on multiples of 64 channels: the gradient that joins at the
+// layer's input (a residual block's skip branch at conv_pre, model.py:26) is the epilogue's residual operand, added in fp32 before the one
+// rounding.  dx_residual must not overlap dx (dx_residual == dx is refused).
+int vcg_conv2d_nhwc_bf16_dgrad_add(const vcg_conv_desc* d, const void* dy, const void* wfrag_t, const void* dx_residual, void* dx,
+                                   hipStream_t stream) {
+    int rc = check_gdesc(d);
+    if (rc) return rc;
+    VCG_CHECK_PTR(dy); VCG_CHECK_PTR(wfrag_t); VCG_CHECK_PTR(dx_residual); VCG_CHECK_PTR(dx);
+    if (d->stride != 1 || d->kh != 3 || d->kw != 3 || d->pad_top != 1 || d->pad_left != 1 || d->cin % 64 || d->cout % 64) return VCG_E_UNSUPPORTED;
+    if (d->oh != d->h || d->ow != d->w) return VCG_E_SHAPE;
+    if (dx_residual == dx) return VCG_E_UNSUPPORTED;
+    GcParams p{};
+    p.x = dy; p.wf = wfrag_t; p.y = dx; p.res = dx_residual;
+    p.wbytes = vcg_conv_frag_bf16_bytes(9, d->cin, d->cout);
+    p.n = d->n; p.ih = d->oh; p.iw = d->ow; p.kch = d->cout;
+    p.oh = d->h; p.ow = d->w; p.mch = d->cin;
+    p.loh = d->h; p.low = d->w; p.osy = p.osx = 1; p.ooy = p.oox = 0;
+    p.isy = p.isx = 1;
+    p.mblocks = d->cin / 32;
+    p.act = VCG_ACT_NONE;
+    for (int ky = 0; ky < 3; ++ky)
+        for (int kx = 0; kx < 3; ++kx) p.taps[p.ntaps++] = GcTap{(short)(1 - ky), (short)(1 - kx), (short)(ky * 3 + kx), 0};
+    return launch_gconv(p, stream);
 }
 
 // y[n][2h][2w][cout] = act(conv_transpose(x) + bias) for Conv2DTranspose(k, strides 2, 'same') (model.py:72): the data gradient of the

@@ -231,6 +231,190 @@ __global__ __launch_bounds__(1024) void wgrad9_reduce_kernel(const float* __rest
     if (tap < 81 && co < 3) dw[(tap * 256 + ci) * 3 + co] = t;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The same weight gradient on 64 input channels: head/conv of make_generator_cyclegan (Conv2D(3, 9, 'same') behind the last
+// 64-channel up-sampling stage).  M = ci = 64 is two 32-channel row tiles, so there are no channel halves: one workgroup reads whole
+// 128-byte pixels, and a wave keeps [2 row tiles] x [3 column tiles] = 96 accumulator registers.  What changes against the kernel above:
+//   * the x tile is [4x32 pixels][64 channels] = 16 KiB of 128-byte pixels.  Consecutive pixels are 128 bytes apart, so pixels q and
+//     q + 2 of a transposed read's four would meet in the same 64-byte bank quarter: the pixel's TWO 64-byte blocks are XORed with
+//     bit 1 of the pixel index, ((q >> 1) & 1), which puts the quarters of pixels 0..3 at {m, m + 2, m ^ 1, (m ^ 1) + 2};
+//   * the tile is 1024 + 240 chunks of 16 bytes: four DMA rounds of x (eight chunks per pixel) and one of dz -- five pieces as above,
+//     but a stage is 20 KiB; the pieces of the tile after next go behind the first five of a k-step's six MFMAs;
+//   * a k-step is 6 MFMAs with 2 + 3 operand-fragment pairs read behind the first five;
+//   * the per-wave dumps are [workgroup][2 row tiles][W9_WAVE_FLOATS], summed in a fixed order by a reduction of their own.
+// dz, its halo, the column tiles and the tap decoding are those of the kernel above.
+constexpr int W6_MT = 2, W6_PX = 128;                            // row tiles per wave; bytes per pixel
+constexpr int W6_XB = W9_TR * W9_TC * W6_PX;                     // 16384
+constexpr int W6_CHUNKS = (W6_XB + W9_DYB) / 16;                 // 1264
+constexpr int W6_NDMA = (W6_CHUNKS + W9_NTH - 1) / W9_NTH;       // 5
+constexpr int W6_BUF = W6_NDMA * W9_NTH * 16;                    // 20480
+static_assert(W9_NS * W6_BUF <= 160 * 1024 && W6_NDMA < 16 && W6_NDMA <= W9_NTW * W6_MT && W6_XB % (W9_NTH * 16) == 0 && W6_XB + W9_DYB <= W6_BUF,
+              "wgrad9 c64: stages / vmcnt / issue slots / regions");
+constexpr int W6_WAIT_ONE_BEHIND = W6_NDMA | 0x0F70;
+constexpr int W6_GRID = 256;                                     // workgroups
+
+__global__ __launch_bounds__(W9_NTH, 1) void wgrad9x9_c64to3_bf16_kernel(W9Params p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int bx = blockIdx.x, nbx = gridDim.x;
+    const unsigned lds0 = (unsigned)(size_t)smem;
+    const long ximg = (long)p.h * p.w_ * W6_PX, dimg = (long)p.h * p.w_ * 8;
+
+    // lane constants of the transposed reads.  A (x): pixel 8*h8 + q (+4t), channels 32*m + 16*((l>>4)&1) + 4*(l&3)
+    const int h8 = (lane >> 5) * 8, q = (lane & 15) >> 2;
+    unsigned abase[W6_MT];
+#pragma unroll
+    for (int m = 0; m < W6_MT; ++m) abase[m] = (unsigned)((h8 + q) * W6_PX + ((m ^ (q >> 1)) << 6) + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2);
+    unsigned bbase[W9_NTW];
+#pragma unroll
+    for (int j = 0; j < W9_NTW; ++j) {
+        int tap = 8 * (wv * W9_NTW + j) + 4 * ((lane >> 4) & 1) + (lane & 3);
+        tap = tap < 81 ? tap : 80;                                  // 15 dummy columns: any address inside the halo (their sums are discarded)
+        const int ky = tap / 9, kx = tap - 9 * ky;
+        bbase[j] = (unsigned)(W6_XB + ((8 - ky) * W9_DC + (8 - kx) + h8 + q) * 8);
+    }
+
+    f32x16 acc[W6_MT][W9_NTW];
+#pragma unroll
+    for (int m = 0; m < W6_MT; ++m)
+#pragma unroll
+        for (int j = 0; j < W9_NTW; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[m][j][e] = 0.f;
+
+    struct Src { int y0, x0; vcg_rsrc rx, rd; };
+    auto decode = [&](int tile) {
+        const int txi = tile % p.tiles_x, t2 = tile / p.tiles_x, tyi = t2 % p.tiles_y, img = t2 / p.tiles_y;
+        return Src{tyi * W9_TR, txi * W9_TC, make_rsrc(p.x + img * ximg, (unsigned long)ximg), make_rsrc(p.dz + img * dimg, (unsigned long)dimg)};
+    };
+    auto dma_piece = [&](const Src& sc, int buf, int k) {
+        const int y0 = sc.y0, x0 = sc.x0;
+        int tid_o = tid;
+        asm volatile("" : "+v"(tid_o));
+        const int s = k * W9_NTH + tid_o;
+        constexpr int KX = W6_XB / (W9_NTH * 16);                       // 4 rounds carry x
+        unsigned off;
+        bool ok;
+        if (k < KX) {                                                   // x: pixel P of the tile, 16-byte position pos of its 128 bytes
+            const int P = s >> 3, pos = s & 7, row = P >> 5, col = P & 31;
+            const int cs = (((pos >> 2) ^ ((P >> 1) & 1)) << 2) | (pos & 3);       // stored position pos holds source chunk cs
+            const int gy = y0 + row, gx = x0 + col;
+            ok = gy < p.h && gx < p.w_;
+            off = (unsigned)(gy * p.w_ + gx) * (unsigned)W6_PX + (unsigned)(cs * 16);
+        } else {                                                        // dz halo: two pixels per 16 bytes (w is even: a pair never straddles a row)
+            const int sd = s - W6_XB / 16, row = (2 * sd) / W9_DC, col = 2 * sd - row * W9_DC;
+            const int gy = y0 - 4 + row, gx = x0 - 4 + col;
+            ok = sd < W9_DYB / 16 && (unsigned)gy < (unsigned)p.h && (unsigned)gx < (unsigned)p.w_;
+            off = (unsigned)(gy * p.w_ + gx) * 8u;
+        }
+        asm volatile("" : "+v"(off));
+        off = ok ? off : VCG_OOB;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(k < KX ? sc.rx : sc.rd,
+                                                 (void __attribute__((address_space(3)))*)(smem + buf * W6_BUF + (k * W9_NTH + wv * 64) * 16), 16, off, 0, 0, 0);
+    };
+
+    unsigned long long fa[2][W6_MT][2], fb[2][W9_NTW][2];
+    auto read_a = [&](unsigned lb, int set, int ks, int m) {
+        const int i = ks >> 1, cb = ks & 1;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) fa[set][m][t] = tr_read(lb + abase[m] + (unsigned)((i * W9_TC + cb * 16 + 4 * t) * W6_PX));
+    };
+    auto read_b = [&](unsigned lb, int set, int ks, int j) {
+        const int i = ks >> 1, cb = ks & 1;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) fb[set][j][t] = tr_read(lb + bbase[j] + (unsigned)((i * W9_DC + cb * 16 + 4 * t) * 8));
+    };
+#define W6_WAIT_SET(S_)                                                                                                                       \
+    asm volatile("s_waitcnt lgkmcnt(0)"                                                                                                       \
+                 : "+v"(fa[S_][0][0]), "+v"(fa[S_][0][1]), "+v"(fa[S_][1][0]), "+v"(fa[S_][1][1]), "+v"(fb[S_][0][0]), "+v"(fb[S_][0][1]),   \
+                   "+v"(fb[S_][1][0]), "+v"(fb[S_][1][1]), "+v"(fb[S_][2][0]), "+v"(fb[S_][2][1]))
+
+    int tile = bx, buf = 0;
+    if (tile < p.total) {
+        const Src first = decode(tile);
+#pragma unroll
+        for (int k = 0; k < W6_NDMA; ++k) dma_piece(first, 0, k);
+    }
+    if (tile + nbx < p.total) {
+        const Src second = decode(tile + nbx);
+#pragma unroll
+        for (int k = 0; k < W6_NDMA; ++k) dma_piece(second, 1, k);
+    }
+    for (; tile < p.total; tile += nbx, buf = buf + 1 == W9_NS ? 0 : buf + 1) {
+        if (tile + nbx < p.total) __builtin_amdgcn_s_waitcnt(W6_WAIT_ONE_BEHIND);
+        else __builtin_amdgcn_s_waitcnt(0x0F70);
+        lds_barrier();
+        const int next = tile + 2 * nbx;
+        const bool has_next = next < p.total;
+        const Src nsrc = decode(has_next ? next : tile);
+        const int nbuf = buf == 0 ? W9_NS - 1 : buf - 1;
+        const unsigned lb = lds0 + buf * W6_BUF;
+#pragma unroll
+        for (int m = 0; m < W6_MT; ++m) read_a(lb, 0, 0, m);
+#pragma unroll
+        for (int j = 0; j < W9_NTW; ++j) read_b(lb, 0, 0, j);
+        W6_WAIT_SET(0);
+        static_for<W9_KS>([&](auto ic) {
+            constexpr int ks = decltype(ic)::value, c = ks & 1, n = c ^ 1;
+#pragma unroll
+            for (int j = 0; j < W9_NTW; ++j) {
+                const u64x2 bv = {fb[c][j][0], fb[c][j][1]};
+                const bf16x8 b = __builtin_bit_cast(bf16x8, bv);
+#pragma unroll
+                for (int m = 0; m < W6_MT; ++m) {
+                    const int u = j * W6_MT + m;                         // MFMA number inside the k-step
+                    const u64x2 av = {fa[c][m][0], fa[c][m][1]};
+                    acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), b, acc[m][j], 0, 0, 0);
+                    if (ks + 1 < W9_KS) {
+                        if (u < W6_MT) read_a(lb, n, ks + 1, u);
+                        else if (u < W6_MT + W9_NTW) read_b(lb, n, ks + 1, u - W6_MT);
+                    }
+                    if (ks == 0 && u < W6_NDMA && has_next) dma_piece(nsrc, nbuf, u);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            if (ks + 1 < W9_KS) {
+                if (n == 0) W6_WAIT_SET(0); else W6_WAIT_SET(1);
+            }
+        });
+    }
+#undef W6_WAIT_SET
+#pragma unroll
+    for (int m = 0; m < W6_MT; ++m) {
+        float* out = p.ws + ((long)bx * W6_MT + m) * W9_WAVE_FLOATS;
+#pragma unroll
+        for (int j = 0; j < W9_NTW; ++j) {
+            const int nt = wv * W9_NTW + j;
+            if (nt < W9_NT) {
+#pragma unroll
+                for (int e = 0; e < 16; ++e) out[(nt * 16 + e) * 64 + lane] = acc[m][j][e];
+            }
+        }
+    }
+}
+
+// the reduction above for the 64-channel dumps [workgroup][2 row tiles][W9_WAVE_FLOATS] -> dW (9,9,64,3)
+__global__ __launch_bounds__(1024) void wgrad9_c64_reduce_kernel(const float* __restrict__ ws, int grid, float* __restrict__ dw) {
+    __shared__ float red[16][64];
+    const int g = threadIdx.x >> 6, cl = threadIdx.x & 63;
+    const int r = blockIdx.x * 64 + cl;                              // raw element: [row tile][W9_WAVE_FLOATS]
+    const int mt = r / W9_WAVE_FLOATS, off = r - mt * W9_WAVE_FLOATS;
+    const float* src = ws + (long)mt * W9_WAVE_FLOATS + off;
+    const long stride = (long)W6_MT * W9_WAVE_FLOATS;
+    float s = 0.f;
+    for (int b = g; b < grid; b += 16) s += src[(long)b * stride];
+    red[g][cl] = s;
+    __syncthreads();
+    if (g != 0) return;
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t += red[i][cl];
+    const int l = off & 63, e = (off >> 6) & 15, nt = off >> 10;
+    const int m = (e & 3) + 8 * (e >> 2) + 4 * (l >> 5), n = l & 31, tap = 8 * nt + (n >> 2), co = n & 3, ci = mt * 32 + m;
+    if (tap < 81 && co < 3) dw[(tap * 64 + ci) * 3 + co] = t;
+}
+
 // dz fp32 NCHW [n][3][h][w] -> bf16 [n][h][w][4] (channel 3 = 0)
 __global__ void pack_dz3_bf16_kernel(const float* __restrict__ dz, __bf16* __restrict__ out, int n, long hw) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -249,30 +433,40 @@ __global__ void pack_dz3_bf16_kernel(const float* __restrict__ dz, __bf16* __res
 extern "C" {
 
 size_t vcg_conv9x9_to3_bf16_wgrad_workspace_bytes(const vcg_conv_desc* d) {
-    if (d == nullptr || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
-    return (size_t)2 * W9_GRID * 4 * W9_WAVE_FLOATS * sizeof(float) + (size_t)d->n * d->h * d->w * 8 + 256;
+    if (d == nullptr || d->n <= 0 || d->h <= 0 || d->w <= 0 || (d->cin != 256 && d->cin != 64)) return 0;
+    const size_t dumps = d->cin == 64 ? (size_t)W6_GRID * W6_MT * W9_WAVE_FLOATS : (size_t)2 * W9_GRID * 4 * W9_WAVE_FLOATS;
+    return dumps * sizeof(float) + (size_t)d->n * d->h * d->w * 8 + 256;
 }
 
 int vcg_conv9x9_to3_bf16_wgrad(const vcg_conv_desc* d, const void* x, const float* dz, float* dw_hwio, void* ws, size_t ws_bytes, hipStream_t stream) {
     VCG_CHECK_PTR(d); VCG_CHECK_PTR(x); VCG_CHECK_PTR(dz); VCG_CHECK_PTR(dw_hwio); VCG_CHECK_PTR(ws);
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->oh != d->h || d->ow != d->w) return VCG_E_SHAPE;
-    if (d->cin != 256 || d->cout != 3 || d->kh != 9 || d->kw != 9 || d->stride != 1 || d->pad_top != 4 || d->pad_left != 4) return VCG_E_UNSUPPORTED;
-    if (d->w % 2 || (long)d->h * d->w * 512 > 0xFFFFFFE0l) return VCG_E_UNSUPPORTED;     // dz pairs must not straddle rows; one image per buffer descriptor
+    if ((d->cin != 256 && d->cin != 64) || d->cout != 3 || d->kh != 9 || d->kw != 9 || d->stride != 1 || d->pad_top != 4 || d->pad_left != 4) return VCG_E_UNSUPPORTED;
+    if (d->w % 2 || (long)d->h * d->w * d->cin * 2 > 0xFFFFFFE0l) return VCG_E_UNSUPPORTED;     // dz pairs must not straddle rows; one image per buffer descriptor
     if (ws_bytes < vcg_conv9x9_to3_bf16_wgrad_workspace_bytes(d)) return VCG_E_WORKSPACE;
+    const bool c64 = d->cin == 64;
     W9Params p;
     p.x = (const unsigned char*)x;
     p.ws = (float*)ws;
-    unsigned char* dzb = (unsigned char*)ws + (size_t)2 * W9_GRID * 4 * W9_WAVE_FLOATS * sizeof(float);
+    unsigned char* dzb = (unsigned char*)ws + (c64 ? (size_t)W6_GRID * W6_MT : (size_t)2 * W9_GRID * 4) * W9_WAVE_FLOATS * sizeof(float);
     dzb += (256 - ((size_t)dzb & 255)) & 255;
     p.dz = dzb;
     p.n = d->n; p.h = d->h; p.w_ = d->w;
     p.tiles_x = ceil_div(d->w, W9_TC);
     p.tiles_y = ceil_div(d->h, W9_TR);
     p.total = p.n * p.tiles_x * p.tiles_y;
-    p.grid = p.total < W9_GRID ? p.total : W9_GRID;
+    p.grid = p.total < (c64 ? W6_GRID : W9_GRID) ? p.total : (c64 ? W6_GRID : W9_GRID);
     const long px = (long)d->n * d->h * d->w;
     pack_dz3_bf16_kernel<<<(unsigned)((px + 255) / 256), 256, 0, stream>>>(dz, (__bf16*)dzb, d->n, (long)d->h * d->w);
     VCG_LAUNCH_CHECK();
+    if (c64) {
+        if (int e = vcg_allow_dyn_lds((const void*)wgrad9x9_c64to3_bf16_kernel, W9_NS * W6_BUF)) return e;
+        wgrad9x9_c64to3_bf16_kernel<<<dim3(p.grid), W9_NTH, W9_NS * W6_BUF, stream>>>(p);
+        VCG_LAUNCH_CHECK();
+        wgrad9_c64_reduce_kernel<<<W6_MT * W9_WAVE_FLOATS / 64, 1024, 0, stream>>>((const float*)ws, p.grid, dw_hwio);
+        VCG_LAUNCH_CHECK();
+        return VCG_OK;
+    }
     if (int e = vcg_allow_dyn_lds((const void*)wgrad9x9_c256to3_bf16_kernel, W9_NS * W9_BUF)) return e;
     wgrad9x9_c256to3_bf16_kernel<<<dim3(2 * p.grid), W9_NTH, W9_NS * W9_BUF, stream>>>(p);
     VCG_LAUNCH_CHECK();

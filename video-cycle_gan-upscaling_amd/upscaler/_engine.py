@@ -906,9 +906,16 @@ class Conv2DBf16(Conv2D):
 
     def backward(self, ctx, dy, need_dx=True, param_grads=True, which=0, dx_residual=None, tag=None, input_lrelu_slope=None):
         """input_lrelu_slope: the layer's input is the OUTPUT of a LeakyReLU with this slope; dx is then multiplied by its derivative, i.e. it
-        is the gradient in front of that activation (the producing layer's backward then needs no activation pass)"""
+        is the gradient in front of that activation (the producing layer's backward then needs no activation pass).
+        dx_residual: a bf16 NHWC gradient that joins at this layer's input (a residual block's skip branch at conv_pre), added in fp32 before
+        the one rounding to bf16 (vcg_conv2d_nhwc_bf16_dgrad_add: 3x3, stride 1)"""
         rt = self.rt
         x, _, d = ctx
+        if dx_residual is not None and need_dx:
+            if dx_residual.dtype != torch.bfloat16 or tuple(dx_residual.shape) != tuple(x.shape):
+                raise TypeError("Conv2DBf16[%s]: dx_residual must be a bf16 NHWC tensor of the input's shape" % self.name)
+            if self.k != 3 or self.stride != 1 or input_lrelu_slope is not None:
+                raise NotImplementedError("Conv2DBf16[%s]: a joining gradient is served for 3x3 stride-1 layers without an input mask" % self.name)
         if param_grads:
             ws, wsn = rt.workspace(rt.lib.vcg_conv2d_nhwc_bf16_wgrad_workspace_bytes(ctypes.byref(d)))
             with Timed(rt, tag and tag + "_wgrad"):
@@ -920,6 +927,11 @@ class Conv2DBf16(Conv2D):
             return None
         _, wd = self._pk.get()
         dx = torch.empty_like(x)
+        if dx_residual is not None:
+            with Timed(rt, tag and tag + "_dgrad_res"):
+                L.check(rt.lib.vcg_conv2d_nhwc_bf16_dgrad_add(ctypes.byref(d), dy.data_ptr(), wd.data_ptr(), dx_residual.data_ptr(), dx.data_ptr(),
+                                                              rt.stream), "vcg_conv2d_nhwc_bf16_dgrad_add[%s]" % self.name)
+            return dx
         with Timed(rt, tag and tag + "_dgrad"):
             L.check(rt.lib.vcg_conv2d_nhwc_bf16_dgrad(ctypes.byref(d), dy.data_ptr(), wd.data_ptr(),
                                                       x.data_ptr() if input_lrelu_slope is not None else None, float(input_lrelu_slope or 0.0),
@@ -1163,15 +1175,17 @@ def f32_to_bf16(rt, x):
 
 class ConvTBf16(ConvT2D):
     """upsampling_block (model.py:70-75) on bf16 NHWC: Conv2DTranspose(k, strides 2) + bias + LeakyReLU for k in {3, 5}, 64 or 256 input
-    channels (the first and the later stages of an x4 generator), out-channels a multiple of 64.  Forward on
+    channels (the first and the later stages of an x4 generator) and k = 3 on 128 (256 -> 128 -> 64 of make_generator_cyclegan, whose
+    stages have no activation of their own), out-channels a multiple of 64.  Forward on
     vcg_conv_transpose2d_nhwc_bf16_fwd.  Backward takes the gradient dz in front of the layer's own activation (the bf16 data gradient of
     final/conv applies the LeakyReLU derivative itself): weight gradient on vcg_conv_transpose2d_nhwc_bf16_wgrad, bias gradient =
     per-channel sum of dz (from the producer's records, or vcg_norm_stats_bf16's shifted sums), data gradient = the stride-2 convolution
     of dz with the kernel read as (in = out-channels, out = in-channels) on vcg_conv2d_nhwc_bf16_fwd."""
 
     def __init__(self, name, cin, cout, k, act=L.ACT_NONE, alpha=0.0):
-        if k not in (3, 5) or cin not in (64, 256) or cout % 64 or cout <= 0 or act not in (L.ACT_NONE, L.ACT_LRELU):
-            raise NotImplementedError("the generic bf16 transposed convolution serves 3x3 / 5x5, 64 or 256 -> 64m channels, no activation or LeakyReLU")
+        if k not in (3, 5) or (cin not in (64, 256) and (cin, k) != (128, 3)) or cout % 64 or cout <= 0 or act not in (L.ACT_NONE, L.ACT_LRELU):
+            raise NotImplementedError("the generic bf16 transposed convolution serves 3x3 / 5x5 on 64 or 256 and 3x3 on 128 input channels, -> 64m "
+                                      "channels, no activation or LeakyReLU")
         super().__init__(name, cin, cout, k, act, alpha)
         self._pk = PackedOperand(self._pack, self)
 
@@ -1332,6 +1346,106 @@ class FinalConv9x9Bf16(Conv2D):
             L.check(rt.lib.vcg_conv9x9_to3_bf16_dgrad(ctypes.byref(d), dy.data_ptr(), wd.data_ptr(),
                                                       x.data_ptr() if input_lrelu_slope is not None else None,
                                                       float(input_lrelu_slope or 0.0), dx.data_ptr(), rt.stream), "vcg_conv9x9_to3_bf16_dgrad")
+        return dx
+
+
+class StemConv9x9Bf16(InitialConv9x9Bf16):
+    """stem/conv of make_generator_cyclegan as a graph node: Conv2D(64, 9, 'same') + bias from the fp32 NCHW frames to bf16 NHWC
+    (vcg_conv9x9_from3_bf16_fwd without activation; the stem/norm node follows and computes its statistics with the separate pass).
+    backward takes the bf16 NHWC gradient the norm's backward returns: weight / bias gradient on vcg_conv3ch_bf16_wgrad (odd widths: the
+    fp32 kernel on an fp32 NCHW copy of it).  The input is the network input: no data gradient."""
+
+    def forward(self, x, residual=None, tag=None):
+        rt = self.rt
+        n, _, h, w = x.shape
+        d = self.desc(n, h, w)
+        z = torch.empty(n, h, w, self.cout, dtype=torch.bfloat16, device=rt.device)
+        with Timed(rt, tag):
+            L.check(rt.lib.vcg_conv9x9_from3_bf16_fwd(ctypes.byref(d), x.data_ptr(), self._pk.get().data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
+                                                      None, z.data_ptr(), rt.stream), "vcg_conv9x9_from3_bf16_fwd[%s]" % self.name)
+        return z, (x, None, d)
+
+    def forward_stats(self, x, instance, tag=None):
+        z, ctx = self.forward(x, tag=tag)
+        return z, ctx, None
+
+    def backward(self, ctx, dz, need_dx=True, param_grads=True, which=0, dx_residual=None, tag=None):
+        rt, lib = self.rt, self.rt.lib
+        x, _, d = ctx
+        if need_dx:
+            raise NotImplementedError("StemConv9x9Bf16[%s] reads the network input: no data gradient" % self.name)
+        if not param_grads:
+            return None
+        need = lib.vcg_conv3ch_bf16_wgrad_workspace_bytes(ctypes.byref(d))
+        if need:
+            ws, wsn = rt.workspace(need)
+            with Timed(rt, tag and tag + "_wgrad"):
+                L.check(lib.vcg_conv3ch_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dz.data_ptr(), self.ps.grad(self.name + "/kernel", which).data_ptr(),
+                                                   self.ps.grad(self.name + "/bias", which).data_ptr(), ws, wsn, rt.stream),
+                        "vcg_conv3ch_bf16_wgrad[%s]" % self.name)
+        else:       # odd widths
+            self._wgrad_fp32(d, x, from_bf16_nhwc(rt, dz), which, True, tag)
+        return None
+
+
+class HeadConv9x9C64Bf16(Conv2D):
+    """head/conv of make_generator_cyclegan: Conv2D(3, 9, 'same') + tanh on a bf16 NHWC input with 64 channels, fp32 NCHW output -- the
+    64-channel counterpart of FinalConv9x9Bf16.  Forward on vcg_conv9x9_c64to3_bf16_fwd; data gradient on vcg_conv9x9_to3_bf16_dgrad with
+    the kernel packed by vcg_pack_conv9x9_3ch_bf16(w, 64, 1) (the 3 -> 64 kernel of the stem with the roles swapped); weight gradient on
+    vcg_conv9x9_to3_bf16_wgrad at cin = 64 (even widths; odd ones take the fp32 kernel on an fp32 NCHW copy of the input)."""
+
+    def __init__(self, name, cin, cout, k, act=L.ACT_TANH):
+        if cin != 64 or cout != 3 or k != 9:
+            raise NotImplementedError("the bf16 head convolution is instantiated for 9x9, 64 -> 3 channels")
+        super().__init__(name, cin, cout, k, 1, "same", act)
+        self._pk = PackedOperand(self._pack, self)
+
+    def _pack(self, out):
+        rt, w = self.rt, self.ps[self.name + "/kernel"]
+        wf, wd = out or (None, _bytes(rt, L.FIRST9X9_WFRAG_BYTES))
+        wf = pack_conv9x9_c64to3_bf16(rt, w, wf)
+        L.check(rt.lib.vcg_pack_conv9x9_3ch_bf16(w.data_ptr(), 64, 1, wd.data_ptr(), rt.stream), "vcg_pack_conv9x9_3ch_bf16")      # data gradient
+        return wf, wd
+
+    def forward(self, x, residual=None, tag=None):
+        rt = self.rt
+        n, h, w, _ = x.shape
+        wf, _ = self._pk.get()
+        d = self.desc(n, h, w)
+        y = rt.empty(n, 3, h, w)
+        with Timed(rt, tag):
+            L.check(rt.lib.vcg_conv9x9_c64to3_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
+                                                       1 if self.act == L.ACT_TANH else 0, y.data_ptr(), rt.stream), "vcg_conv9x9_c64to3_bf16_fwd")
+        return y, (x, y, d)
+
+    def backward(self, ctx, dy, need_dx=True, param_grads=True, which=0, dx_residual=None, tag=None):
+        """dy fp32 NCHW; returns dx as bf16 NHWC"""
+        rt = self.rt
+        x, y, d = ctx
+        if dx_residual is not None:
+            raise NotImplementedError("HeadConv9x9C64Bf16[%s]: no gradient joins at the head's input" % self.name)
+        db_done = self.act != L.ACT_NONE
+        if db_done:
+            dy = act_bwd_bias(self, y, dy, d, param_grads, which)
+        if param_grads and d.w % 2 == 0:
+            ws, wsn = rt.workspace(max(rt.lib.vcg_conv9x9_to3_bf16_wgrad_workspace_bytes(ctypes.byref(d)),
+                                       rt.lib.vcg_channel_sum_workspace_bytes(d.n, 3, d.oh * d.ow)))
+            with Timed(rt, tag and tag + "_wgrad"):
+                L.check(rt.lib.vcg_conv9x9_to3_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dy.data_ptr(), self.ps.grad(self.name + "/kernel", which).data_ptr(),
+                                                          ws, wsn, rt.stream), "vcg_conv9x9_to3_bf16_wgrad[%s]" % self.name)
+            if not db_done:
+                L.check(rt.lib.vcg_channel_sum(dy.data_ptr(), d.n, 3, d.oh * d.ow, self.ps.grad(self.name + "/bias", which).data_ptr(), ws, wsn,
+                                               rt.stream), "vcg_channel_sum[%s]" % self.name)
+        elif param_grads:
+            # odd widths: the fp32 kernel on an fp32 NCHW copy of the input (exact conversion)
+            self._wgrad_fp32(d, from_bf16_nhwc(rt, x), dy, which, not db_done, tag)
+        if not need_dx:
+            return None
+        _, wd = self._pk.get()
+        dx = torch.empty_like(x)
+        with Timed(rt, tag and tag + "_dgrad"):
+            L.check(rt.lib.vcg_conv9x9_to3_bf16_dgrad(ctypes.byref(d), dy.data_ptr(), wd.data_ptr(), None, 0.0, dx.data_ptr(), rt.stream),
+                    "vcg_conv9x9_to3_bf16_dgrad[%s]" % self.name)
         return dx
 
 

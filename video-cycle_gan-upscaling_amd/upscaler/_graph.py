@@ -503,6 +503,9 @@ def build_model(inputs, outputs, name="model", seed=7):
             if nid in grads:
                 if grads[nid] is dx:
                     return
+                if grads[nid].dtype != E.torch.float32 or dx.dtype != E.torch.float32:
+                    # vcg_axpby adds fp32 words; a bf16 gradient joins through a layer's dx_residual operand instead
+                    raise TypeError("two gradients meet at node %d in %s / %s: only fp32 gradients are accumulated here" % (nid, grads[nid].dtype, dx.dtype))
                 # never write into a tensor another branch may still hold: accumulate into the new one
                 E.axpby(self.rt, grads[nid], dx, 1.0, 1.0)
             grads[nid] = dx
@@ -564,8 +567,13 @@ def _attention_bf16(net):
     return Bf16AttentionGenerator(net)
 
 
+CYCLEGAN_BF16_SERVED = "bf16 training of make_generator_cyclegan is instantiated for filters=64 on 3-channel (RGB) frames, norm 'instance' or " \
+                       "'batch', kernel_size 3, n_downsample 1 or 2 and upscale_factor 1, 2 or 4 (any res_block_num); use dtype='fp32' for " \
+                       "other shapes"
+
+
 def make_generator_cyclegan(output_image_shape, filters=64, n_downsample=2, res_block_num=9, upscale_factor=1, norm="instance",
-                            kernel_size=3, seed=7):
+                            kernel_size=3, seed=7, dtype="fp32"):
     """BASELINE.json north_star's literal generator shape (SURVEY.md section 8 row a11, "canonical down-sampling CycleGAN generator";
     the reference itself only ships up-scalers): down-sampling convolutions -> residual blocks -> transposed-convolution up-sampling,
 
@@ -576,32 +584,66 @@ def make_generator_cyclegan(output_image_shape, filters=64, n_downsample=2, res_
         Conv 9x9 (3) + tanh                                                 head
 
     written on the reference's functional block API.  norm: 'instance' (north_star) or 'batch'; PReLU slopes start at 0 (= ReLU).
-    upscale_factor 1 maps a frame to a frame (CycleGAN); 2 / 4 make it an up-scaler like the reference's."""
+    upscale_factor 1 maps a frame to a frame (CycleGAN); 2 / 4 make it an up-scaler like the reference's.
+
+    dtype='bf16' (the keyword of the discriminator factories): every activation between stem/conv's output and head/conv's input is stored
+    bf16 NHWC, in training and in learning phase 0; master weights, gradients, statistics, moving averages, PReLU and norm parameters stay
+    fp32, layer names and parameter layouts are those of the fp32 model.  Frames go in and come out as fp32 NCHW.  CYCLEGAN_BF16_SERVED
+    lists the shapes; others raise NotImplementedError."""
     f = int(upscale_factor)
     if f < 1 or f & (f - 1):
         raise ValueError("upscale_factor must be a power of two")
+    if dtype not in ("fp32", "bf16"):
+        raise ValueError(dtype)
+    bf = dtype == "bf16"
+    if bf and (filters != 64 or output_image_shape[2] != 3 or norm not in ("instance", "batch") or kernel_size != 3 or n_downsample not in (1, 2)
+               or f not in (1, 2, 4)):
+        raise NotImplementedError(CYCLEGAN_BF16_SERVED)
     in_shape = (output_image_shape[0] // f, output_image_shape[1] // f, output_image_shape[2])
     if in_shape[0] % (1 << n_downsample) or in_shape[1] % (1 << n_downsample):
         raise ValueError("input %s is not divisible by 2**n_downsample" % (in_shape,))
     inp = Input(shape=in_shape, name="stem/input")
-    model = conv2d(inp, filters, 9, 1, "same", name="stem/conv")
-    model = batch_norm_prelu(model, name="stem/norm", prelu_name="stem/prelu", norm=norm)
-    ch = filters
-    for i in range(n_downsample):
-        ch *= 2
-        model = conv2d(model, ch, kernel_size, 2, "same", name="down/%d/conv" % i)
-        model = batch_norm_prelu(model, name="down/%d/norm" % i, prelu_name="down/%d/prelu" % i, norm=norm)
-    for i in range(res_block_num):
-        model = residual_block(model, kernel_size, ch, 1, name="res_block/%d" % i, norm=norm)
-    for i in range(n_downsample + int(math.log(f, 2))):
-        ch = max(ch // 2, filters)
-        model = conv2d_transpose(model, ch, kernel_size, 2, name="up/%d/conv_transp" % i)
-        model = batch_norm_prelu(model, name="up/%d/norm" % i, prelu_name="up/%d/prelu" % i, norm=norm)
-    model = conv2d(model, 3, 9, 1, "same", activation="tanh", name="head/conv")
+    if bf:
+        # the same graph on the bf16 layer classes: GraphModel passes values and gradients between nodes without looking inside them
+        node = lambda t, kind, layer, c: KTensor(t.graph, t.graph.add(kind, layer, [t.nid]), c)
+        conv = lambda t, c, s, name: node(t, "conv", E.Conv2DBf16(name, t.channels, c, kernel_size, s), c)
+        norm_prelu = lambda t, name, pname: node(t, "norm", E.NormActBf16(name, t.channels, norm, L.ACT_PRELU, prelu_name=pname), t.channels)
+        model = norm_prelu(node(inp, "conv", E.StemConv9x9Bf16("stem/conv", 3, filters, 9), filters), "stem/norm", "stem/prelu")
+        ch = filters
+        for i in range(n_downsample):
+            ch *= 2
+            model = norm_prelu(conv(model, ch, 2, "down/%d/conv" % i), "down/%d/norm" % i, "down/%d/prelu" % i)
+        for i in range(res_block_num):
+            n, gen = "res_block/%d" % i, model
+            model = norm_prelu(conv(model, ch, 1, n + "/conv_pre"), n + "/batch_norm_pre", n + "/prelu")
+            model = node(conv(model, ch, 1, n + "/conv_post"), "norm", E.NormActBf16(n + "/batch_norm_post", ch, norm), ch)
+            model = add([gen, model], name=n + "/final_add")          # fused into batch_norm_post's kernel
+        for i in range(n_downsample + int(math.log(f, 2))):
+            cout = max(ch // 2, filters)
+            model = node(model, "convt", E.ConvTBf16("up/%d/conv_transp" % i, ch, cout, kernel_size), cout)
+            ch = cout
+            model = norm_prelu(model, "up/%d/norm" % i, "up/%d/prelu" % i)
+        model = node(model, "conv", E.HeadConv9x9C64Bf16("head/conv", ch, 3, 9), 3)
+    else:
+        model = conv2d(inp, filters, 9, 1, "same", name="stem/conv")
+        model = batch_norm_prelu(model, name="stem/norm", prelu_name="stem/prelu", norm=norm)
+        ch = filters
+        for i in range(n_downsample):
+            ch *= 2
+            model = conv2d(model, ch, kernel_size, 2, "same", name="down/%d/conv" % i)
+            model = batch_norm_prelu(model, name="down/%d/norm" % i, prelu_name="down/%d/prelu" % i, norm=norm)
+        for i in range(res_block_num):
+            model = residual_block(model, kernel_size, ch, 1, name="res_block/%d" % i, norm=norm)
+        for i in range(n_downsample + int(math.log(f, 2))):
+            ch = max(ch // 2, filters)
+            model = conv2d_transpose(model, ch, kernel_size, 2, name="up/%d/conv_transp" % i)
+            model = batch_norm_prelu(model, name="up/%d/norm" % i, prelu_name="up/%d/prelu" % i, norm=norm)
+        model = conv2d(model, 3, 9, 1, "same", activation="tanh", name="head/conv")
     net = build_model(inp, model, name="generator_cyclegan", seed=seed)
     # what the bf16 inference engine recognises the topology by (not the name string), and its entry point
     net.cyclegan_generator = {"filters": filters, "n_downsample": n_downsample, "res_block_num": res_block_num, "upscale_factor": f, "norm": norm,
                               "kernel_size": kernel_size, "channels": output_image_shape[2]}
+    net.dtype = dtype
     net.to_inference_bf16 = lambda: _cyclegan_bf16(net)
     return net
 
