@@ -15,49 +15,79 @@
 //     in 192 accumulator registers for the whole launch (why this shape: see the k-loop); tiles stream by `buffer_load ... lds` through a ring of three stages, one barrier per tile; the
 //     operand fragments of the next k-step are read behind the MFMAs of this one;
 //   * per-wave partial blocks go to the workspace as raw register dumps and are summed in a fixed order (deterministic).
+//
+// The same kernel on 64 input channels is head/conv of make_generator_cyclegan (Conv2D(3, 9, 'same') behind the last 64-channel
+// up-sampling stage).  M = 64 is two row tiles, so there are no channel halves: one workgroup reads whole 128-byte pixels, a wave keeps
+// 2 x 3 tiles = 96 accumulator registers and a k-step is 6 MFMAs with 2 + 3 fragment pairs read behind the first five.  Beyond W9Cfg:
+//   * consecutive pixels are 128 bytes apart in LDS, so pixels q and q + 2 of a transposed read's four would meet in the same 64-byte
+//     bank quarter: the pixel's TWO 64-byte blocks are XORed with bit 1 of the pixel index, ((q >> 1) & 1), which puts the quarters
+//     of pixels 0..3 at {m, m + 2, m ^ 1, (m ^ 1) + 2};
+//   * the tile is 1024 + 240 chunks of 16 bytes: four DMA rounds of x and one of dz, a stage of 20 KiB (256 channels: nine pieces,
+//     36 KiB); the five pieces of the tile after next go behind the first five MFMAs of k-step 0.
 #include "vcg_common.hpp"
 
 namespace {
 
 constexpr int W9_TR = 4, W9_TC = 32, W9_NT = 11;
-constexpr int W9_NWV = 4, W9_NTH = W9_NWV * 64;                  // waves = quarters of the (11 + 1 dummy) column tiles; a wave holds ALL four row tiles
-constexpr int W9_NTW = 3, W9_MT = 4;                             // column tiles / row tiles (32 channels) per wave
-constexpr int W9_XB = W9_TR * W9_TC * 256;                       // 32768: x tile, 128 channels
+constexpr int W9_NWV = 4, W9_NTH = W9_NWV * 64;                  // waves = quarters of the (11 + 1 dummy) column tiles; a wave holds ALL row tiles
+constexpr int W9_NTW = 3;                                        // column tiles per wave
 constexpr int W9_DR = W9_TR + 8, W9_DC = W9_TC + 8;              // dz halo: 12 x 40 pixels of 8 bytes
 constexpr int W9_DYB = W9_DR * W9_DC * 8;                        // 3840
-constexpr int W9_CHUNKS = (W9_XB + W9_DYB) / 16;                 // 2288
-constexpr int W9_NDMA = (W9_CHUNKS + W9_NTH - 1) / W9_NTH;       // 5
-constexpr int W9_BUF = W9_NDMA * W9_NTH * 16;                    // 40960
 constexpr int W9_NS = 3;                                         // ring of three stages: two tiles in flight while one is multiplied
 constexpr int W9_KS = W9_TR * W9_TC / 16;                        // k-steps of 16 pixels per tile
-static_assert(W9_NS * W9_BUF <= 160 * 1024 && W9_NDMA < 16 && W9_NDMA <= W9_NTW * W9_MT && W9_XB % (W9_NTH * 16) == 0, "wgrad9: stages / vmcnt / issue slots / regions");
-constexpr int W9_WAIT_ONE_BEHIND = W9_NDMA | 0x0F70;             // s_waitcnt vmcnt(NDMA): all but the youngest stage's pieces have landed
-constexpr int W9_GRID = 128;                                     // workgroups per channel half
 constexpr int W9_WAVE_FLOATS = W9_NT * 16 * 64;
+static_assert(W9_WAVE_FLOATS % 64 == 0, "wgrad9 reduce: 64 raw elements per block stay inside one wave block");
+
+// per input-channel count: row tiles (32 channels) per wave, bytes per pixel in LDS (one channel half) and in memory, channel halves,
+// workgroups per half
+template <int CIN> struct W9Cfg;
+template <> struct W9Cfg<256> { static constexpr int MT = 4, PX = 256, SRC_PX = 512, HALVES = 2, GRID = 128; };
+template <> struct W9Cfg<64> { static constexpr int MT = 2, PX = 128, SRC_PX = 128, HALVES = 1, GRID = 256; };
+
+template <int CIN> struct W9 : W9Cfg<CIN> {
+    using C = W9Cfg<CIN>;
+    static constexpr int CPP_LOG2 = C::PX == 256 ? 4 : 3;                    // 16-byte chunks per LDS pixel: 16 / 8
+    static constexpr int SWZ = C::MT == 4 ? 0 : 1;                           // a pixel's MT 64-byte blocks are XORed with (pixel >> SWZ) & (MT - 1)
+    static constexpr int XB = W9_TR * W9_TC * C::PX;                         // x tile: 32768 / 16384
+    static constexpr int NDMA = ((XB + W9_DYB) / 16 + W9_NTH - 1) / W9_NTH;  // 1-KiB pieces per tile: 9 / 5
+    static constexpr int BUF = NDMA * W9_NTH * 16;                           // 36864 / 20480
+    static constexpr int WAIT_ONE_BEHIND = NDMA | 0x0F70;                    // s_waitcnt vmcnt(NDMA): all but the youngest stage's pieces have landed
+    static constexpr size_t DUMP_FLOATS = (size_t)C::HALVES * C::GRID * C::MT * W9_WAVE_FLOATS;
+    static_assert(C::PX == 16 << CPP_LOG2 && C::PX == 64 * C::MT && C::SRC_PX == C::PX * C::HALVES && C::SRC_PX == CIN * 2, "wgrad9: pixel layout");
+    static_assert(W9_NS * BUF <= 160 * 1024 && NDMA < 16 && NDMA <= W9_NTW * C::MT && XB % (W9_NTH * 16) == 0 && XB + W9_DYB <= BUF,
+                  "wgrad9: stages / vmcnt / issue slots / regions");
+};
 
 struct W9Params {
-    const unsigned char* x;      // bf16 NHWC [n][h][w][256]
+    const unsigned char* x;      // bf16 NHWC [n][h][w][CIN]
     const unsigned char* dz;     // bf16 [n][h][w][4] (channel 3 = 0)
-    float* ws;                   // [2 halves][grid][4 waves][W9_WAVE_FLOATS]
+    float* ws;                   // [halves][grid][row tiles][W9_WAVE_FLOATS]
     int n, h, w_, tiles_x, tiles_y, total, grid;
 };
 
-__global__ __launch_bounds__(W9_NTH, 1) void wgrad9x9_c256to3_bf16_kernel(W9Params p) {
+// a tile's origin and descriptors.  Not a local class of the kernel template: with the descriptor members the host pass then drops the
+// kernel's stub without a diagnostic and the library fails to load (undefined symbol)
+struct W9Src { int y0, x0; vcg_rsrc rx, rd; };
+
+template <int CIN>
+__global__ __launch_bounds__(W9_NTH, 1) void wgrad9x9_to3_bf16_kernel(W9Params p) {
+    using K = W9<CIN>;
+    constexpr int MT = K::MT, PX = K::PX, HS = K::HALVES - 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     // channel half mh (input channels 128*mh ..) is the FASTEST index of the grid: the two workgroups that read the two 256-byte halves of
     // the same 512-byte pixels start together and stay in step, so a DRAM page is opened once for both (with the half as the slow index
     // the halves of a page were fetched at unrelated times: 3.0 TB/s whatever the tile pipeline looked like)
-    const int mh = blockIdx.x & 1, bx = blockIdx.x >> 1, nbx = gridDim.x >> 1;
+    const int mh = blockIdx.x & HS, bx = blockIdx.x >> HS, nbx = gridDim.x >> HS;
     const unsigned lds0 = (unsigned)(size_t)smem;
-    const long ximg = (long)p.h * p.w_ * 512, dimg = (long)p.h * p.w_ * 8;
+    const long ximg = (long)p.h * p.w_ * K::SRC_PX, dimg = (long)p.h * p.w_ * 8;
 
     // lane constants of the transposed reads.  A (x): pixel 8*h8 + q (+4t), channels 32*m + 16*((l>>4)&1) + 4*(l&3) .. of the half
     const int h8 = (lane >> 5) * 8, q = (lane & 15) >> 2;
-    unsigned abase[W9_MT];
+    unsigned abase[MT];
 #pragma unroll
-    for (int m = 0; m < W9_MT; ++m) abase[m] = (unsigned)((h8 + q) * 256 + ((m ^ q) << 6) + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2);
+    for (int m = 0; m < MT; ++m) abase[m] = (unsigned)((h8 + q) * PX + ((m ^ (q >> K::SWZ)) << 6) + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2);
     // B (dz): lane L of a 16-group addresses pixel (L >> 2) of the k-quad, shifted for tap 8*nt + 4*((lane>>4)&1) + (L & 3), nt = 3*wv + j
     unsigned bbase[W9_NTW];
 #pragma unroll
@@ -65,39 +95,40 @@ __global__ __launch_bounds__(W9_NTH, 1) void wgrad9x9_c256to3_bf16_kernel(W9Para
         int tap = 8 * (wv * W9_NTW + j) + 4 * ((lane >> 4) & 1) + (lane & 3);
         tap = tap < 81 ? tap : 80;                                  // 15 dummy columns: any address inside the halo (their sums are discarded)
         const int ky = tap / 9, kx = tap - 9 * ky;
-        bbase[j] = (unsigned)(W9_XB + ((8 - ky) * W9_DC + (8 - kx) + h8 + q) * 8);
+        bbase[j] = (unsigned)(K::XB + ((8 - ky) * W9_DC + (8 - kx) + h8 + q) * 8);
     }
 
-    f32x16 acc[W9_MT][W9_NTW];
+    f32x16 acc[MT][W9_NTW];
 #pragma unroll
-    for (int m = 0; m < W9_MT; ++m)
+    for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int j = 0; j < W9_NTW; ++j)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[m][j][e] = 0.f;
 
     // one 1-KiB piece (DMA round k) of a tile's stage; the tile's origin and descriptors are decoded once per tile (scalars)
-    struct Src { int y0, x0; vcg_rsrc rx, rd; };
     auto decode = [&](int tile) {
         const int txi = tile % p.tiles_x, t2 = tile / p.tiles_x, tyi = t2 % p.tiles_y, img = t2 / p.tiles_y;
-        return Src{tyi * W9_TR, txi * W9_TC, make_rsrc(p.x + img * ximg, (unsigned long)ximg), make_rsrc(p.dz + img * dimg, (unsigned long)dimg)};
+        return W9Src{tyi * W9_TR, txi * W9_TC, make_rsrc(p.x + img * ximg, (unsigned long)ximg), make_rsrc(p.dz + img * dimg, (unsigned long)dimg)};
     };
-    auto dma_piece = [&](const Src& sc, int buf, int k) {
+    auto dma_piece = [&](const W9Src& sc, int buf, int k) {
         const int y0 = sc.y0, x0 = sc.x0;
         int tid_o = tid;
         asm volatile("" : "+v"(tid_o));                                 // keep the slot arithmetic inside the tile loop (no hoisted registers)
         const int s = k * W9_NTH + tid_o;
-        constexpr int KX = W9_XB / (W9_NTH * 16);                       // rounds that carry x
+        constexpr int KX = K::XB / (W9_NTH * 16);                       // rounds that carry x
         unsigned off;
         bool ok;
-        if (k < KX) {                                                   // x: pixel P of the tile, 16-byte position pos of its 256 bytes
-            const int P = s >> 4, pos = s & 15, row = P >> 5, col = P & 31;
-            const int cs = (((pos >> 2) ^ (P & 3)) << 2) | (pos & 3);              // stored position pos holds source chunk cs
+        if (k < KX) {                                                   // x: pixel P of the tile, 16-byte position pos of its PX bytes
+            const int P = s >> K::CPP_LOG2, pos = s & (PX / 16 - 1), row = P >> 5, col = P & 31;   // a shift: s is signed, s / CPP costs sign fix-ups
+            const int cs = (((pos >> 2) ^ ((P >> K::SWZ) & (MT - 1))) << 2) | (pos & 3);         // stored position pos holds source chunk cs
             const int gy = y0 + row, gx = x0 + col;
             ok = gy < p.h && gx < p.w_;
-            off = (unsigned)(gy * p.w_ + gx) * 512u + (unsigned)(mh * 256 + cs * 16);
+            // two spellings of one offset: with mh folded to 0 the compiler orders the address arithmetic of the later pieces differently
+            if constexpr (K::HALVES == 2) off = (unsigned)(gy * p.w_ + gx) * 512u + (unsigned)(mh * 256 + cs * 16);
+            else off = (unsigned)(gy * p.w_ + gx) * (unsigned)PX + (unsigned)(cs * 16);
         } else {                                                        // dz halo: two pixels per 16 bytes (w is even: a pair never straddles a row)
-            const int sd = s - W9_XB / 16, row = (2 * sd) / W9_DC, col = 2 * sd - row * W9_DC;
+            const int sd = s - K::XB / 16, row = (2 * sd) / W9_DC, col = 2 * sd - row * W9_DC;
             const int gy = y0 - 4 + row, gx = x0 - 4 + col;
             ok = sd < W9_DYB / 16 && (unsigned)gy < (unsigned)p.h && (unsigned)gx < (unsigned)p.w_;
             off = (unsigned)(gy * p.w_ + gx) * 8u;
@@ -105,7 +136,7 @@ __global__ __launch_bounds__(W9_NTH, 1) void wgrad9x9_c256to3_bf16_kernel(W9Para
         asm volatile("" : "+v"(off));
         off = ok ? off : VCG_OOB;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(k < KX ? sc.rx : sc.rd,
-                                                 (void __attribute__((address_space(3)))*)(smem + buf * W9_BUF + (k * W9_NTH + wv * 64) * 16), 16, off, 0, 0, 0);
+                                                 (void __attribute__((address_space(3)))*)(smem + buf * K::BUF + (k * W9_NTH + wv * 64) * 16), 16, off, 0, 0, 0);
     };
 
     // What bounds this kernel is the LDS pipe: a ds_read_b64_tr_b16 occupies it for ~8 cycles, an MFMA its SIMD's matrix pipe for 32, and a
@@ -115,46 +146,52 @@ __global__ __launch_bounds__(W9_NTH, 1) void wgrad9x9_c256to3_bf16_kernel(W9Para
     // and CU either way.  Here a wave holds ALL four row tiles x 3 of the 12 column tiles (192 accumulator registers): 4 x 14 = 56
     // reads per k-step and CU for the same 48 MFMAs.  The fragments of k-step ks + 1 are read behind the MFMAs of k-step ks (a pair of
     // reads after each of the first seven), the 9 DMA pieces of the tile after next behind the first MFMAs of k-step 0.
-    unsigned long long fa[2][W9_MT][2], fb[2][W9_NTW][2];
+    unsigned long long fa[2][MT][2], fb[2][W9_NTW][2];
     auto read_a = [&](unsigned lb, int set, int ks, int m) {
         const int i = ks >> 1, cb = ks & 1;
 #pragma unroll
-        for (int t = 0; t < 2; ++t) fa[set][m][t] = tr_read(lb + abase[m] + (unsigned)((i * W9_TC + cb * 16 + 4 * t) * 256));
+        for (int t = 0; t < 2; ++t) fa[set][m][t] = tr_read(lb + abase[m] + (unsigned)((i * W9_TC + cb * 16 + 4 * t) * PX));
     };
     auto read_b = [&](unsigned lb, int set, int ks, int j) {
         const int i = ks >> 1, cb = ks & 1;
 #pragma unroll
         for (int t = 0; t < 2; ++t) fb[set][j][t] = tr_read(lb + bbase[j] + (unsigned)((i * W9_DC + cb * 16 + 4 * t) * 8));
     };
+    // an asm operand list cannot be looped: one list per row-tile count
 #define W9_WAIT_SET(S_)                                                                                                                       \
-    asm volatile("s_waitcnt lgkmcnt(0)"                                                                                                       \
-                 : "+v"(fa[S_][0][0]), "+v"(fa[S_][0][1]), "+v"(fa[S_][1][0]), "+v"(fa[S_][1][1]), "+v"(fa[S_][2][0]), "+v"(fa[S_][2][1]),   \
-                   "+v"(fa[S_][3][0]), "+v"(fa[S_][3][1]), "+v"(fb[S_][0][0]), "+v"(fb[S_][0][1]), "+v"(fb[S_][1][0]), "+v"(fb[S_][1][1]),   \
-                   "+v"(fb[S_][2][0]), "+v"(fb[S_][2][1]))
+    if constexpr (MT == 4)                                                                                                                    \
+        asm volatile("s_waitcnt lgkmcnt(0)"                                                                                                   \
+                     : "+v"(fa[S_][0][0]), "+v"(fa[S_][0][1]), "+v"(fa[S_][1][0]), "+v"(fa[S_][1][1]), "+v"(fa[S_][2][0]), "+v"(fa[S_][2][1]), \
+                       "+v"(fa[S_][3][0]), "+v"(fa[S_][3][1]), "+v"(fb[S_][0][0]), "+v"(fb[S_][0][1]), "+v"(fb[S_][1][0]), "+v"(fb[S_][1][1]), \
+                       "+v"(fb[S_][2][0]), "+v"(fb[S_][2][1]));                                                                                \
+    else                                                                                                                                      \
+        asm volatile("s_waitcnt lgkmcnt(0)"                                                                                                   \
+                     : "+v"(fa[S_][0][0]), "+v"(fa[S_][0][1]), "+v"(fa[S_][1][0]), "+v"(fa[S_][1][1]), "+v"(fb[S_][0][0]), "+v"(fb[S_][0][1]), \
+                       "+v"(fb[S_][1][0]), "+v"(fb[S_][1][1]), "+v"(fb[S_][2][0]), "+v"(fb[S_][2][1]))
 
     int tile = bx, buf = 0;
     if (tile < p.total) {
-        const Src first = decode(tile);
+        const W9Src first = decode(tile);
 #pragma unroll
-        for (int k = 0; k < W9_NDMA; ++k) dma_piece(first, 0, k);
+        for (int k = 0; k < K::NDMA; ++k) dma_piece(first, 0, k);
     }
     if (tile + nbx < p.total) {
-        const Src second = decode(tile + nbx);
+        const W9Src second = decode(tile + nbx);
 #pragma unroll
-        for (int k = 0; k < W9_NDMA; ++k) dma_piece(second, 1, k);
+        for (int k = 0; k < K::NDMA; ++k) dma_piece(second, 1, k);
     }
     for (; tile < p.total; tile += nbx, buf = buf + 1 == W9_NS ? 0 : buf + 1) {
         // a wave's loads retire in order: "at most NDMA outstanding" = this tile's stage is complete, the next one's may still be in flight
-        if (tile + nbx < p.total) __builtin_amdgcn_s_waitcnt(W9_WAIT_ONE_BEHIND);
+        if (tile + nbx < p.total) __builtin_amdgcn_s_waitcnt(K::WAIT_ONE_BEHIND);
         else __builtin_amdgcn_s_waitcnt(0x0F70);
         lds_barrier();                                // ... and everyone else's part; the stage multiplied last is free again
         const int next = tile + 2 * nbx;
         const bool has_next = next < p.total;
-        const Src nsrc = decode(has_next ? next : tile);
+        const W9Src nsrc = decode(has_next ? next : tile);
         const int nbuf = buf == 0 ? W9_NS - 1 : buf - 1;
-        const unsigned lb = lds0 + buf * W9_BUF;
+        const unsigned lb = lds0 + buf * K::BUF;
 #pragma unroll
-        for (int m = 0; m < W9_MT; ++m) read_a(lb, 0, 0, m);
+        for (int m = 0; m < MT; ++m) read_a(lb, 0, 0, m);
 #pragma unroll
         for (int j = 0; j < W9_NTW; ++j) read_b(lb, 0, 0, j);
         W9_WAIT_SET(0);
@@ -166,28 +203,28 @@ __global__ __launch_bounds__(W9_NTH, 1) void wgrad9x9_c256to3_bf16_kernel(W9Para
                 const u64x2 bv = {fb[c][j][0], fb[c][j][1]};
                 const bf16x8 b = __builtin_bit_cast(bf16x8, bv);
 #pragma unroll
-                for (int m = 0; m < W9_MT; ++m) {
-                    const int u = j * W9_MT + m;                         // MFMA number inside the k-step
+                for (int m = 0; m < MT; ++m) {
+                    const int u = j * MT + m;                            // MFMA number inside the k-step
                     const u64x2 av = {fa[c][m][0], fa[c][m][1]};
                     acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), b, acc[m][j], 0, 0, 0);
                     if (ks + 1 < W9_KS) {
-                        if (u < W9_MT) read_a(lb, n, ks + 1, u);
-                        else if (u < W9_MT + W9_NTW) read_b(lb, n, ks + 1, u - W9_MT);
+                        if (u < MT) read_a(lb, n, ks + 1, u);
+                        else if (u < MT + W9_NTW) read_b(lb, n, ks + 1, u - MT);
                     }
-                    if (ks == 0 && u < W9_NDMA && has_next) dma_piece(nsrc, nbuf, u);
+                    if (ks == 0 && u < K::NDMA && has_next) dma_piece(nsrc, nbuf, u);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
             if (ks + 1 < W9_KS) {
-                if (n == 0) W9_WAIT_SET(0); else W9_WAIT_SET(1);
+                if (n == 0) { W9_WAIT_SET(0); } else { W9_WAIT_SET(1); }
             }
         });
     }
 #undef W9_WAIT_SET
     // raw register dumps into the row tiles' blocks (coalesced); decoded by the reduction
 #pragma unroll
-    for (int m = 0; m < W9_MT; ++m) {
-        float* out = p.ws + (((long)mh * p.grid + bx) * 4 + m) * W9_WAVE_FLOATS;
+    for (int m = 0; m < MT; ++m) {
+        float* out = p.ws + (((long)mh * p.grid + bx) * MT + m) * W9_WAVE_FLOATS;
 #pragma unroll
         for (int j = 0; j < W9_NTW; ++j) {
             const int nt = wv * W9_NTW + j;
@@ -202,13 +239,15 @@ __global__ __launch_bounds__(W9_NTH, 1) void wgrad9x9_c256to3_bf16_kernel(W9Para
 // dW[tap][ci][co] = sum over workgroups, in a fixed order, of the wave blocks.  block = 64 consecutive RAW dump elements x 16 record lanes
 // (coalesced reads, eight records in flight per thread, fixed-order combine through LDS); the decoded (tap, ci, co) position is only used
 // for the single store.  (One thread per OUTPUT element walking all records read scattered words one latency after the other: 47 us.)
+template <int CIN>
 __global__ __launch_bounds__(1024) void wgrad9_reduce_kernel(const float* __restrict__ ws, int grid, float* __restrict__ dw) {
+    constexpr int MT = W9<CIN>::MT;
     __shared__ float red[16][64];
     const int g = threadIdx.x >> 6, cl = threadIdx.x & 63;
     const int r = blockIdx.x * 64 + cl;                              // raw element: [channel half][row tile][W9_WAVE_FLOATS]
-    const int mh = r / (4 * W9_WAVE_FLOATS), rem = r - mh * 4 * W9_WAVE_FLOATS, mt = rem / W9_WAVE_FLOATS, off = rem - mt * W9_WAVE_FLOATS;
-    const float* src = ws + (((long)mh * grid) * 4 + mt) * W9_WAVE_FLOATS + off;
-    const long stride = 4l * W9_WAVE_FLOATS;
+    const int mh = r / (MT * W9_WAVE_FLOATS), rem = r - mh * MT * W9_WAVE_FLOATS, mt = rem / W9_WAVE_FLOATS, off = rem - mt * W9_WAVE_FLOATS;
+    const float* src = ws + (((long)mh * grid) * MT + mt) * W9_WAVE_FLOATS + off;
+    const long stride = (long)MT * W9_WAVE_FLOATS;
     float s = 0.f;
     int b = g;
     for (; b + 16 * 7 < grid; b += 16 * 8) {
@@ -228,191 +267,7 @@ __global__ __launch_bounds__(1024) void wgrad9_reduce_kernel(const float* __rest
     // raw offset -> column tile nt, register e, lane l;  D[row][col]: row = (e&3) + 8*(e>>2) + 4*(l>>5), col = l&31 = (tap slot, co)
     const int l = off & 63, e = (off >> 6) & 15, nt = off >> 10;
     const int m = (e & 3) + 8 * (e >> 2) + 4 * (l >> 5), n = l & 31, tap = 8 * nt + (n >> 2), co = n & 3, ci = mh * 128 + mt * 32 + m;
-    if (tap < 81 && co < 3) dw[(tap * 256 + ci) * 3 + co] = t;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// The same weight gradient on 64 input channels: head/conv of make_generator_cyclegan (Conv2D(3, 9, 'same') behind the last
-// 64-channel up-sampling stage).  M = ci = 64 is two 32-channel row tiles, so there are no channel halves: one workgroup reads whole
-// 128-byte pixels, and a wave keeps [2 row tiles] x [3 column tiles] = 96 accumulator registers.  What changes against the kernel above:
-//   * the x tile is [4x32 pixels][64 channels] = 16 KiB of 128-byte pixels.  Consecutive pixels are 128 bytes apart, so pixels q and
-//     q + 2 of a transposed read's four would meet in the same 64-byte bank quarter: the pixel's TWO 64-byte blocks are XORed with
-//     bit 1 of the pixel index, ((q >> 1) & 1), which puts the quarters of pixels 0..3 at {m, m + 2, m ^ 1, (m ^ 1) + 2};
-//   * the tile is 1024 + 240 chunks of 16 bytes: four DMA rounds of x (eight chunks per pixel) and one of dz -- five pieces as above,
-//     but a stage is 20 KiB; the pieces of the tile after next go behind the first five of a k-step's six MFMAs;
-//   * a k-step is 6 MFMAs with 2 + 3 operand-fragment pairs read behind the first five;
-//   * the per-wave dumps are [workgroup][2 row tiles][W9_WAVE_FLOATS], summed in a fixed order by a reduction of their own.
-// dz, its halo, the column tiles and the tap decoding are those of the kernel above.
-constexpr int W6_MT = 2, W6_PX = 128;                            // row tiles per wave; bytes per pixel
-constexpr int W6_XB = W9_TR * W9_TC * W6_PX;                     // 16384
-constexpr int W6_CHUNKS = (W6_XB + W9_DYB) / 16;                 // 1264
-constexpr int W6_NDMA = (W6_CHUNKS + W9_NTH - 1) / W9_NTH;       // 5
-constexpr int W6_BUF = W6_NDMA * W9_NTH * 16;                    // 20480
-static_assert(W9_NS * W6_BUF <= 160 * 1024 && W6_NDMA < 16 && W6_NDMA <= W9_NTW * W6_MT && W6_XB % (W9_NTH * 16) == 0 && W6_XB + W9_DYB <= W6_BUF,
-              "wgrad9 c64: stages / vmcnt / issue slots / regions");
-constexpr int W6_WAIT_ONE_BEHIND = W6_NDMA | 0x0F70;
-constexpr int W6_GRID = 256;                                     // workgroups
-
-__global__ __launch_bounds__(W9_NTH, 1) void wgrad9x9_c64to3_bf16_kernel(W9Params p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int bx = blockIdx.x, nbx = gridDim.x;
-    const unsigned lds0 = (unsigned)(size_t)smem;
-    const long ximg = (long)p.h * p.w_ * W6_PX, dimg = (long)p.h * p.w_ * 8;
-
-    // lane constants of the transposed reads.  A (x): pixel 8*h8 + q (+4t), channels 32*m + 16*((l>>4)&1) + 4*(l&3)
-    const int h8 = (lane >> 5) * 8, q = (lane & 15) >> 2;
-    unsigned abase[W6_MT];
-#pragma unroll
-    for (int m = 0; m < W6_MT; ++m) abase[m] = (unsigned)((h8 + q) * W6_PX + ((m ^ (q >> 1)) << 6) + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2);
-    unsigned bbase[W9_NTW];
-#pragma unroll
-    for (int j = 0; j < W9_NTW; ++j) {
-        int tap = 8 * (wv * W9_NTW + j) + 4 * ((lane >> 4) & 1) + (lane & 3);
-        tap = tap < 81 ? tap : 80;                                  // 15 dummy columns: any address inside the halo (their sums are discarded)
-        const int ky = tap / 9, kx = tap - 9 * ky;
-        bbase[j] = (unsigned)(W6_XB + ((8 - ky) * W9_DC + (8 - kx) + h8 + q) * 8);
-    }
-
-    f32x16 acc[W6_MT][W9_NTW];
-#pragma unroll
-    for (int m = 0; m < W6_MT; ++m)
-#pragma unroll
-        for (int j = 0; j < W9_NTW; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][j][e] = 0.f;
-
-    struct Src { int y0, x0; vcg_rsrc rx, rd; };
-    auto decode = [&](int tile) {
-        const int txi = tile % p.tiles_x, t2 = tile / p.tiles_x, tyi = t2 % p.tiles_y, img = t2 / p.tiles_y;
-        return Src{tyi * W9_TR, txi * W9_TC, make_rsrc(p.x + img * ximg, (unsigned long)ximg), make_rsrc(p.dz + img * dimg, (unsigned long)dimg)};
-    };
-    auto dma_piece = [&](const Src& sc, int buf, int k) {
-        const int y0 = sc.y0, x0 = sc.x0;
-        int tid_o = tid;
-        asm volatile("" : "+v"(tid_o));
-        const int s = k * W9_NTH + tid_o;
-        constexpr int KX = W6_XB / (W9_NTH * 16);                       // 4 rounds carry x
-        unsigned off;
-        bool ok;
-        if (k < KX) {                                                   // x: pixel P of the tile, 16-byte position pos of its 128 bytes
-            const int P = s >> 3, pos = s & 7, row = P >> 5, col = P & 31;
-            const int cs = (((pos >> 2) ^ ((P >> 1) & 1)) << 2) | (pos & 3);       // stored position pos holds source chunk cs
-            const int gy = y0 + row, gx = x0 + col;
-            ok = gy < p.h && gx < p.w_;
-            off = (unsigned)(gy * p.w_ + gx) * (unsigned)W6_PX + (unsigned)(cs * 16);
-        } else {                                                        // dz halo: two pixels per 16 bytes (w is even: a pair never straddles a row)
-            const int sd = s - W6_XB / 16, row = (2 * sd) / W9_DC, col = 2 * sd - row * W9_DC;
-            const int gy = y0 - 4 + row, gx = x0 - 4 + col;
-            ok = sd < W9_DYB / 16 && (unsigned)gy < (unsigned)p.h && (unsigned)gx < (unsigned)p.w_;
-            off = (unsigned)(gy * p.w_ + gx) * 8u;
-        }
-        asm volatile("" : "+v"(off));
-        off = ok ? off : VCG_OOB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(k < KX ? sc.rx : sc.rd,
-                                                 (void __attribute__((address_space(3)))*)(smem + buf * W6_BUF + (k * W9_NTH + wv * 64) * 16), 16, off, 0, 0, 0);
-    };
-
-    unsigned long long fa[2][W6_MT][2], fb[2][W9_NTW][2];
-    auto read_a = [&](unsigned lb, int set, int ks, int m) {
-        const int i = ks >> 1, cb = ks & 1;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) fa[set][m][t] = tr_read(lb + abase[m] + (unsigned)((i * W9_TC + cb * 16 + 4 * t) * W6_PX));
-    };
-    auto read_b = [&](unsigned lb, int set, int ks, int j) {
-        const int i = ks >> 1, cb = ks & 1;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) fb[set][j][t] = tr_read(lb + bbase[j] + (unsigned)((i * W9_DC + cb * 16 + 4 * t) * 8));
-    };
-#define W6_WAIT_SET(S_)                                                                                                                       \
-    asm volatile("s_waitcnt lgkmcnt(0)"                                                                                                       \
-                 : "+v"(fa[S_][0][0]), "+v"(fa[S_][0][1]), "+v"(fa[S_][1][0]), "+v"(fa[S_][1][1]), "+v"(fb[S_][0][0]), "+v"(fb[S_][0][1]),   \
-                   "+v"(fb[S_][1][0]), "+v"(fb[S_][1][1]), "+v"(fb[S_][2][0]), "+v"(fb[S_][2][1]))
-
-    int tile = bx, buf = 0;
-    if (tile < p.total) {
-        const Src first = decode(tile);
-#pragma unroll
-        for (int k = 0; k < W6_NDMA; ++k) dma_piece(first, 0, k);
-    }
-    if (tile + nbx < p.total) {
-        const Src second = decode(tile + nbx);
-#pragma unroll
-        for (int k = 0; k < W6_NDMA; ++k) dma_piece(second, 1, k);
-    }
-    for (; tile < p.total; tile += nbx, buf = buf + 1 == W9_NS ? 0 : buf + 1) {
-        if (tile + nbx < p.total) __builtin_amdgcn_s_waitcnt(W6_WAIT_ONE_BEHIND);
-        else __builtin_amdgcn_s_waitcnt(0x0F70);
-        lds_barrier();
-        const int next = tile + 2 * nbx;
-        const bool has_next = next < p.total;
-        const Src nsrc = decode(has_next ? next : tile);
-        const int nbuf = buf == 0 ? W9_NS - 1 : buf - 1;
-        const unsigned lb = lds0 + buf * W6_BUF;
-#pragma unroll
-        for (int m = 0; m < W6_MT; ++m) read_a(lb, 0, 0, m);
-#pragma unroll
-        for (int j = 0; j < W9_NTW; ++j) read_b(lb, 0, 0, j);
-        W6_WAIT_SET(0);
-        static_for<W9_KS>([&](auto ic) {
-            constexpr int ks = decltype(ic)::value, c = ks & 1, n = c ^ 1;
-#pragma unroll
-            for (int j = 0; j < W9_NTW; ++j) {
-                const u64x2 bv = {fb[c][j][0], fb[c][j][1]};
-                const bf16x8 b = __builtin_bit_cast(bf16x8, bv);
-#pragma unroll
-                for (int m = 0; m < W6_MT; ++m) {
-                    const int u = j * W6_MT + m;                         // MFMA number inside the k-step
-                    const u64x2 av = {fa[c][m][0], fa[c][m][1]};
-                    acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), b, acc[m][j], 0, 0, 0);
-                    if (ks + 1 < W9_KS) {
-                        if (u < W6_MT) read_a(lb, n, ks + 1, u);
-                        else if (u < W6_MT + W9_NTW) read_b(lb, n, ks + 1, u - W6_MT);
-                    }
-                    if (ks == 0 && u < W6_NDMA && has_next) dma_piece(nsrc, nbuf, u);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            if (ks + 1 < W9_KS) {
-                if (n == 0) W6_WAIT_SET(0); else W6_WAIT_SET(1);
-            }
-        });
-    }
-#undef W6_WAIT_SET
-#pragma unroll
-    for (int m = 0; m < W6_MT; ++m) {
-        float* out = p.ws + ((long)bx * W6_MT + m) * W9_WAVE_FLOATS;
-#pragma unroll
-        for (int j = 0; j < W9_NTW; ++j) {
-            const int nt = wv * W9_NTW + j;
-            if (nt < W9_NT) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) out[(nt * 16 + e) * 64 + lane] = acc[m][j][e];
-            }
-        }
-    }
-}
-
-// the reduction above for the 64-channel dumps [workgroup][2 row tiles][W9_WAVE_FLOATS] -> dW (9,9,64,3)
-__global__ __launch_bounds__(1024) void wgrad9_c64_reduce_kernel(const float* __restrict__ ws, int grid, float* __restrict__ dw) {
-    __shared__ float red[16][64];
-    const int g = threadIdx.x >> 6, cl = threadIdx.x & 63;
-    const int r = blockIdx.x * 64 + cl;                              // raw element: [row tile][W9_WAVE_FLOATS]
-    const int mt = r / W9_WAVE_FLOATS, off = r - mt * W9_WAVE_FLOATS;
-    const float* src = ws + (long)mt * W9_WAVE_FLOATS + off;
-    const long stride = (long)W6_MT * W9_WAVE_FLOATS;
-    float s = 0.f;
-    for (int b = g; b < grid; b += 16) s += src[(long)b * stride];
-    red[g][cl] = s;
-    __syncthreads();
-    if (g != 0) return;
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) t += red[i][cl];
-    const int l = off & 63, e = (off >> 6) & 15, nt = off >> 10;
-    const int m = (e & 3) + 8 * (e >> 2) + 4 * (l >> 5), n = l & 31, tap = 8 * nt + (n >> 2), co = n & 3, ci = mt * 32 + m;
-    if (tap < 81 && co < 3) dw[(tap * 64 + ci) * 3 + co] = t;
+    if (tap < 81 && co < 3) dw[(tap * CIN + ci) * 3 + co] = t;
 }
 
 // dz fp32 NCHW [n][3][h][w] -> bf16 [n][h][w][4] (channel 3 = 0)
@@ -428,13 +283,39 @@ __global__ void pack_dz3_bf16_kernel(const float* __restrict__ dz, __bf16* __res
     *(bf16x4*)(out + i * 4) = v;
 }
 
+// workspace: the dumps, then (256-byte aligned) the packed dz
+template <int CIN>
+int wgrad9_launch(const vcg_conv_desc* d, const void* x, const float* dz, float* dw_hwio, void* ws, hipStream_t stream) {
+    using K = W9<CIN>;
+    W9Params p;
+    p.x = (const unsigned char*)x;
+    p.ws = (float*)ws;
+    unsigned char* dzb = (unsigned char*)ws + K::DUMP_FLOATS * sizeof(float);
+    dzb += (256 - ((size_t)dzb & 255)) & 255;
+    p.dz = dzb;
+    p.n = d->n; p.h = d->h; p.w_ = d->w;
+    p.tiles_x = ceil_div(d->w, W9_TC);
+    p.tiles_y = ceil_div(d->h, W9_TR);
+    p.total = p.n * p.tiles_x * p.tiles_y;
+    p.grid = p.total < K::GRID ? p.total : K::GRID;
+    const long px = (long)d->n * d->h * d->w;
+    pack_dz3_bf16_kernel<<<(unsigned)((px + 255) / 256), 256, 0, stream>>>(dz, (__bf16*)dzb, d->n, (long)d->h * d->w);
+    VCG_LAUNCH_CHECK();
+    if (int e = vcg_allow_dyn_lds((const void*)wgrad9x9_to3_bf16_kernel<CIN>, W9_NS * K::BUF)) return e;
+    wgrad9x9_to3_bf16_kernel<CIN><<<dim3(K::HALVES * p.grid), W9_NTH, W9_NS * K::BUF, stream>>>(p);
+    VCG_LAUNCH_CHECK();
+    wgrad9_reduce_kernel<CIN><<<K::HALVES * K::MT * W9_WAVE_FLOATS / 64, 1024, 0, stream>>>((const float*)ws, p.grid, dw_hwio);
+    VCG_LAUNCH_CHECK();
+    return VCG_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t vcg_conv9x9_to3_bf16_wgrad_workspace_bytes(const vcg_conv_desc* d) {
     if (d == nullptr || d->n <= 0 || d->h <= 0 || d->w <= 0 || (d->cin != 256 && d->cin != 64)) return 0;
-    const size_t dumps = d->cin == 64 ? (size_t)W6_GRID * W6_MT * W9_WAVE_FLOATS : (size_t)2 * W9_GRID * 4 * W9_WAVE_FLOATS;
+    const size_t dumps = d->cin == 64 ? W9<64>::DUMP_FLOATS : W9<256>::DUMP_FLOATS;
     return dumps * sizeof(float) + (size_t)d->n * d->h * d->w * 8 + 256;
 }
 
@@ -444,36 +325,7 @@ int vcg_conv9x9_to3_bf16_wgrad(const vcg_conv_desc* d, const void* x, const floa
     if ((d->cin != 256 && d->cin != 64) || d->cout != 3 || d->kh != 9 || d->kw != 9 || d->stride != 1 || d->pad_top != 4 || d->pad_left != 4) return VCG_E_UNSUPPORTED;
     if (d->w % 2 || (long)d->h * d->w * d->cin * 2 > 0xFFFFFFE0l) return VCG_E_UNSUPPORTED;     // dz pairs must not straddle rows; one image per buffer descriptor
     if (ws_bytes < vcg_conv9x9_to3_bf16_wgrad_workspace_bytes(d)) return VCG_E_WORKSPACE;
-    const bool c64 = d->cin == 64;
-    W9Params p;
-    p.x = (const unsigned char*)x;
-    p.ws = (float*)ws;
-    unsigned char* dzb = (unsigned char*)ws + (c64 ? (size_t)W6_GRID * W6_MT : (size_t)2 * W9_GRID * 4) * W9_WAVE_FLOATS * sizeof(float);
-    dzb += (256 - ((size_t)dzb & 255)) & 255;
-    p.dz = dzb;
-    p.n = d->n; p.h = d->h; p.w_ = d->w;
-    p.tiles_x = ceil_div(d->w, W9_TC);
-    p.tiles_y = ceil_div(d->h, W9_TR);
-    p.total = p.n * p.tiles_x * p.tiles_y;
-    p.grid = p.total < (c64 ? W6_GRID : W9_GRID) ? p.total : (c64 ? W6_GRID : W9_GRID);
-    const long px = (long)d->n * d->h * d->w;
-    pack_dz3_bf16_kernel<<<(unsigned)((px + 255) / 256), 256, 0, stream>>>(dz, (__bf16*)dzb, d->n, (long)d->h * d->w);
-    VCG_LAUNCH_CHECK();
-    if (c64) {
-        if (int e = vcg_allow_dyn_lds((const void*)wgrad9x9_c64to3_bf16_kernel, W9_NS * W6_BUF)) return e;
-        wgrad9x9_c64to3_bf16_kernel<<<dim3(p.grid), W9_NTH, W9_NS * W6_BUF, stream>>>(p);
-        VCG_LAUNCH_CHECK();
-        wgrad9_c64_reduce_kernel<<<W6_MT * W9_WAVE_FLOATS / 64, 1024, 0, stream>>>((const float*)ws, p.grid, dw_hwio);
-        VCG_LAUNCH_CHECK();
-        return VCG_OK;
-    }
-    if (int e = vcg_allow_dyn_lds((const void*)wgrad9x9_c256to3_bf16_kernel, W9_NS * W9_BUF)) return e;
-    wgrad9x9_c256to3_bf16_kernel<<<dim3(2 * p.grid), W9_NTH, W9_NS * W9_BUF, stream>>>(p);
-    VCG_LAUNCH_CHECK();
-    static_assert(W9_WAVE_FLOATS % 64 == 0, "wgrad9 reduce: 64 raw elements per block stay inside one wave block");
-    wgrad9_reduce_kernel<<<2 * 4 * W9_WAVE_FLOATS / 64, 1024, 0, stream>>>((const float*)ws, p.grid, dw_hwio);
-    VCG_LAUNCH_CHECK();
-    return VCG_OK;
+    return d->cin == 64 ? wgrad9_launch<64>(d, x, dz, dw_hwio, ws, stream) : wgrad9_launch<256>(d, x, dz, dw_hwio, ws, stream);
 }
 
 }  // extern "C"

@@ -859,6 +859,60 @@ def fold_batch(rt, pairs):
     return {id(cv): (out[0, i], out[1, i]) for i, (cv, nm) in enumerate(pairs)}
 
 
+def conv_nhwc_bf16_fwd(layer, x, tag, instance=None):
+    """y = conv(x) + bias on vcg_conv2d_nhwc_bf16_fwd, for a layer whose _pk holds (forward, data gradient) fragments.  instance True /
+    False: on vcg_conv2d_nhwc_bf16_fwd_stats, which also leaves the statistics partials of y for the instance / batch normalisation
+    behind the layer -- where the tiled kernel serves the shape; where it does not, the plain forward (the caller then runs the separate
+    statistics pass).  Returns (y, d, stats) with stats = (records buffer, records per group) or None."""
+    rt = layer.rt
+    n, h, w, _ = x.shape
+    d = layer.desc(n, h, w)
+    nrec = 0
+    if instance is not None:
+        nrec = rt.lib.vcg_conv2d_nhwc_bf16_stats_records(ctypes.byref(d), L.STATS_INSTANCE if instance else L.STATS_BATCH)
+    wf, _ = layer._pk.get()
+    y = _bf16(rt, n, d.oh, d.ow, layer.cout)
+    bias = layer.ps[layer.name + "/bias"].data_ptr()
+    if nrec <= 0:
+        with Timed(rt, tag):
+            L.check(rt.lib.vcg_conv2d_nhwc_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), bias, L.ACT_NONE, 0.0, y.data_ptr(), rt.stream),
+                    "vcg_conv2d_nhwc_bf16_fwd[%s]" % layer.name)
+        return y, d, None
+    buf = rt.empty((n if instance else 1) * nrec * 2 * layer.cout)
+    with Timed(rt, tag):
+        L.check(rt.lib.vcg_conv2d_nhwc_bf16_fwd_stats(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), bias, y.data_ptr(), buf.data_ptr(), rt.stream),
+                "vcg_conv2d_nhwc_bf16_fwd_stats[%s]" % layer.name)
+    return y, d, (buf, nrec)
+
+
+def conv_nhwc_bf16_wgrad(layer, d, x, dy, which, tag):
+    """weight / bias gradient (fp32, into the master gradient) of the convolution d from bf16 NHWC x and dy on vcg_conv2d_nhwc_bf16_wgrad"""
+    rt = layer.rt
+    ws, wsn = rt.workspace(rt.lib.vcg_conv2d_nhwc_bf16_wgrad_workspace_bytes(ctypes.byref(d)))
+    with Timed(rt, tag and tag + "_wgrad"):
+        L.check(rt.lib.vcg_conv2d_nhwc_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dy.data_ptr(), layer.ps.grad(layer.name + "/kernel", which).data_ptr(),
+                                                  layer.ps.grad(layer.name + "/bias", which).data_ptr(), ws, wsn, rt.stream),
+                "vcg_conv2d_nhwc_bf16_wgrad[%s]" % layer.name)
+
+
+def conv3ch_bf16_wgrad(layer, d, x, dz, which, tag, need=None):
+    """weight / bias gradient of a layer on the 3-channel fp32 NCHW frames x from the bf16 NHWC gradient dz: vcg_conv3ch_bf16_wgrad (frames
+    and gradient as bf16 MFMA operands), or at odd widths -- the kernel then asks for no workspace -- the fp32 kernel on an fp32 NCHW copy
+    of dz, which is returned (None otherwise).  need: the workspace size where the caller has already asked for it."""
+    rt = layer.rt
+    need = rt.lib.vcg_conv3ch_bf16_wgrad_workspace_bytes(ctypes.byref(d)) if need is None else need
+    if not need:
+        dz32 = from_bf16_nhwc(rt, dz)
+        layer._wgrad_fp32(d, x, dz32, which, True, tag)
+        return dz32
+    ws, wsn = rt.workspace(need)
+    with Timed(rt, tag and tag + "_wgrad"):
+        L.check(rt.lib.vcg_conv3ch_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dz.data_ptr(), layer.ps.grad(layer.name + "/kernel", which).data_ptr(),
+                                              layer.ps.grad(layer.name + "/bias", which).data_ptr(), ws, wsn, rt.stream),
+                "vcg_conv3ch_bf16_wgrad[%s]" % layer.name)
+    return None
+
+
 class Conv2DBf16(Conv2D):
     """keras.layers.Conv2D on bf16 NHWC activations, the discriminators' shapes (3x3 / 4x4, stride 1 / 2, channel counts that
     are multiples of 64 -- what the bf16 weight gradient serves): forward and data gradient on vcg_conv2d_nhwc_bf16_* (weights re-laid out as MFMA operand
@@ -876,33 +930,13 @@ class Conv2DBf16(Conv2D):
         self._pk = PackedOperand(lambda out: pack_conv_frag_bf16_pair(self.rt, self.ps[self.name + "/kernel"], k * k, cin, cout, out), self)
 
     def forward(self, x, residual=None, tag=None):
-        rt = self.rt
-        n, h, w, _ = x.shape
-        d = self.desc(n, h, w)
-        wf, _ = self._pk.get()
-        y = torch.empty(n, d.oh, d.ow, self.cout, dtype=torch.bfloat16, device=rt.device)
-        with Timed(rt, tag):
-            L.check(rt.lib.vcg_conv2d_nhwc_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
-                                                    L.ACT_NONE, 0.0, y.data_ptr(), rt.stream), "vcg_conv2d_nhwc_bf16_fwd[%s]" % self.name)
+        y, d, _ = conv_nhwc_bf16_fwd(self, x, tag)
         return y, (x, None, d)
 
     def forward_stats(self, x, instance, tag=None):
         """forward + per-tile statistics partials of the output (see Conv3x3Bf16.forward_stats)"""
-        rt = self.rt
-        n, h, w, _ = x.shape
-        d = self.desc(n, h, w)
-        mode = L.STATS_INSTANCE if instance else L.STATS_BATCH
-        nrec = rt.lib.vcg_conv2d_nhwc_bf16_stats_records(ctypes.byref(d), mode)
-        if nrec <= 0:
-            y, ctx = self.forward(x, tag=tag)
-            return y, ctx, None
-        wf, _ = self._pk.get()
-        y = torch.empty(n, d.oh, d.ow, self.cout, dtype=torch.bfloat16, device=rt.device)
-        buf = rt.empty((n if instance else 1) * nrec * 2 * self.cout)
-        with Timed(rt, tag):
-            L.check(rt.lib.vcg_conv2d_nhwc_bf16_fwd_stats(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
-                                                          y.data_ptr(), buf.data_ptr(), rt.stream), "vcg_conv2d_nhwc_bf16_fwd_stats[%s]" % self.name)
-        return y, (x, None, d), (buf, nrec)
+        y, d, stats = conv_nhwc_bf16_fwd(self, x, tag, instance)
+        return y, (x, None, d), stats
 
     def backward(self, ctx, dy, need_dx=True, param_grads=True, which=0, dx_residual=None, tag=None, input_lrelu_slope=None):
         """input_lrelu_slope: the layer's input is the OUTPUT of a LeakyReLU with this slope; dx is then multiplied by its derivative, i.e. it
@@ -917,12 +951,7 @@ class Conv2DBf16(Conv2D):
             if self.k != 3 or self.stride != 1 or input_lrelu_slope is not None:
                 raise NotImplementedError("Conv2DBf16[%s]: a joining gradient is served for 3x3 stride-1 layers without an input mask" % self.name)
         if param_grads:
-            ws, wsn = rt.workspace(rt.lib.vcg_conv2d_nhwc_bf16_wgrad_workspace_bytes(ctypes.byref(d)))
-            with Timed(rt, tag and tag + "_wgrad"):
-                L.check(rt.lib.vcg_conv2d_nhwc_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dy.data_ptr(),
-                                                          self.ps.grad(self.name + "/kernel", which).data_ptr(),
-                                                          self.ps.grad(self.name + "/bias", which).data_ptr(), ws, wsn, rt.stream),
-                        "vcg_conv2d_nhwc_bf16_wgrad[%s]" % self.name)
+            conv_nhwc_bf16_wgrad(self, d, x, dy, which, tag)
         if not need_dx:
             return None
         _, wd = self._pk.get()
@@ -957,45 +986,20 @@ class Conv5x5Bf16(TrunkConvBf16):
         return pack_conv_frag_bf16(self.rt, w, 25, 64, 64, 0, wf), pack_conv_frag_bf16(self.rt, w, 25, 64, 64, 2, wd)
 
     def forward(self, x, tag=None):
-        rt = self.rt
-        n, h, w, _ = x.shape
-        d = self.desc(n, h, w)
-        wf, _ = self._pk.get()
-        y = torch.empty(n, h, w, 64, dtype=torch.bfloat16, device=rt.device)
-        with Timed(rt, tag):
-            L.check(rt.lib.vcg_conv2d_nhwc_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
-                                                    L.ACT_NONE, 0.0, y.data_ptr(), rt.stream), "vcg_conv2d_nhwc_bf16_fwd[%s]" % self.name)
+        y, d, _ = conv_nhwc_bf16_fwd(self, x, tag)
         return y, (x, d)
 
     def forward_stats(self, x, instance, tag=None):
         """forward + per-tile statistics partials of the output (see Conv3x3Bf16.forward_stats); None where the tiled kernel does not
         serve the shape (the caller then runs the separate statistics pass)"""
-        rt = self.rt
-        n, h, w, _ = x.shape
-        d = self.desc(n, h, w)
-        nrec = rt.lib.vcg_conv2d_nhwc_bf16_stats_records(ctypes.byref(d), L.STATS_INSTANCE if instance else L.STATS_BATCH)
-        if nrec <= 0:
-            y, ctx = self.forward(x, tag)
-            return y, ctx, None
-        wf, _ = self._pk.get()
-        y = torch.empty(n, h, w, 64, dtype=torch.bfloat16, device=rt.device)
-        buf = rt.empty((n if instance else 1) * nrec * 2 * 64)
-        with Timed(rt, tag):
-            L.check(rt.lib.vcg_conv2d_nhwc_bf16_fwd_stats(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
-                                                          y.data_ptr(), buf.data_ptr(), rt.stream), "vcg_conv2d_nhwc_bf16_fwd_stats[%s]" % self.name)
-        return y, (x, d), (buf, nrec)
+        y, d, stats = conv_nhwc_bf16_fwd(self, x, tag, instance)
+        return y, (x, d), stats
 
     def backward(self, ctx, dy, need_dx=True, param_grads=True, which=0, dx_residual=None, tag=None):
         """dx_residual: a gradient that joins at this layer's input (the block's skip branch), added in the epilogue"""
-        rt = self.rt
         x, d = ctx
         if param_grads:
-            ws, wsn = rt.workspace(rt.lib.vcg_conv2d_nhwc_bf16_wgrad_workspace_bytes(ctypes.byref(d)))
-            with Timed(rt, tag and tag + "_wgrad"):
-                L.check(rt.lib.vcg_conv2d_nhwc_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dy.data_ptr(),
-                                                          self.ps.grad(self.name + "/kernel", which).data_ptr(),
-                                                          self.ps.grad(self.name + "/bias", which).data_ptr(), ws, wsn, rt.stream),
-                        "vcg_conv2d_nhwc_bf16_wgrad[%s]" % self.name)
+            conv_nhwc_bf16_wgrad(self, d, x, dy, which, tag)
         return self._dgrad(d, dy, dx_residual, tag) if need_dx else None
 
 
@@ -1042,7 +1046,6 @@ class InitialConv9x9Bf16(Conv2D):
         nrec = lib.vcg_prelu_bwd_nhwc_bf16_records(d.n, hw)
         L.check(min(nrec, 0), "vcg_prelu_bwd_nhwc_bf16_records")
         rec = rt.empty(nrec * self.cout)
-        gk, gb = self.ps.grad(self.name + "/kernel", which), self.ps.grad(self.name + "/bias", which)
         need = lib.vcg_conv3ch_bf16_wgrad_workspace_bytes(ctypes.byref(d))
         if need:
             # dz stays bf16 NHWC: the weight gradient multiplies it as an MFMA operand (vcg_conv3ch_bf16_wgrad)
@@ -1050,10 +1053,7 @@ class InitialConv9x9Bf16(Conv2D):
             L.check(lib.vcg_prelu_bwd_nhwc_bf16_to_bf16(d1.data_ptr(), _ptr(d2), z.data_ptr(), alpha.data_ptr(), d.n, self.cout, hw, dz.data_ptr(),
                                                         rec.data_ptr(), rt.stream), "vcg_prelu_bwd_nhwc_bf16_to_bf16")
             L.check(lib.vcg_sum_records(rec.data_ptr(), nrec, self.cout, 1.0, dalpha.data_ptr(), rt.stream), "vcg_sum_records[%s]" % self.name)
-            ws, wsn = rt.workspace(need)
-            with Timed(rt, tag and tag + "_wgrad"):
-                L.check(lib.vcg_conv3ch_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dz.data_ptr(), gk.data_ptr(), gb.data_ptr(), ws, wsn, rt.stream),
-                        "vcg_conv3ch_bf16_wgrad[%s]" % self.name)
+            conv3ch_bf16_wgrad(self, d, x, dz, which, tag, need)
             return
         # odd widths: the fp32 weight-gradient kernel on the fp32 NCHW form of dz
         dz = rt.empty(d.n, self.cout, d.h, d.w)
@@ -1093,18 +1093,7 @@ class FirstConvBf16(Conv2D):
         """dz: bf16 NHWC gradient in front of the activation"""
         rt = self.rt
         x, _, d = ctx
-        dz32 = None
-        if param_grads:
-            gk, gb = self.ps.grad(self.name + "/kernel", which), self.ps.grad(self.name + "/bias", which)
-            need = rt.lib.vcg_conv3ch_bf16_wgrad_workspace_bytes(ctypes.byref(d))
-            if need:
-                ws, wsn = rt.workspace(need)
-                with Timed(rt, tag and tag + "_wgrad"):
-                    L.check(rt.lib.vcg_conv3ch_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dz.data_ptr(), gk.data_ptr(), gb.data_ptr(), ws, wsn, rt.stream),
-                            "vcg_conv3ch_bf16_wgrad[%s]" % self.name)
-            else:       # odd widths: the fp32 weight-gradient kernel on an fp32 NCHW copy of dz
-                dz32 = from_bf16_nhwc(rt, dz)
-                self._wgrad_fp32(d, x, dz32, which, True, tag)
+        dz32 = conv3ch_bf16_wgrad(self, d, x, dz, which, tag) if param_grads else None
         if not need_dx:
             return None
         dx = rt.empty(d.n, self.cin, d.h, d.w)
@@ -1275,23 +1264,25 @@ class ConvT3x3Bf16(ConvTBf16):
         return y, (x, y, d)
 
 
-class FinalConv9x9Bf16(Conv2D):
-    """final/conv (model.py:290-291): Conv2D(3, 9) + tanh on a bf16 NHWC input with 256 channels, fp32 NCHW output.  Forward on
-    vcg_conv9x9_to3_bf16_fwd; data gradient on vcg_conv9x9_to3_bf16_dgrad, which also applies the derivative of the LeakyReLU that
-    produced the input (so the result is the gradient in front of that activation); weight gradient on vcg_conv9x9_to3_bf16_wgrad
-    (even widths; odd ones take the fp32 kernel on an fp32 NCHW copy of the input)."""
+class Conv9x9To3Bf16(Conv2D):
+    """Conv2D(3, 9, 'same') + tanh on a bf16 NHWC input with CIN channels, fp32 NCHW output: final/conv (model.py:290-291) on 256 channels
+    and head/conv of make_generator_cyclegan on 64.  Forward on the entry point FWD over the operand PACK_FWD lays out; data gradient on
+    vcg_conv9x9_to3_bf16_dgrad with the kernel packed by vcg_pack_conv9x9_3ch_bf16(w, CIN, 1) into DGRAD_PACK_BYTES (the 3 -> 64 kernel of
+    the first layer with the roles swapped, once per 64 channels); weight gradient on vcg_conv9x9_to3_bf16_wgrad (even widths; odd ones take
+    the fp32 kernel on an fp32 NCHW copy of the input).  INPUT_ACT: whether backward serves input_lrelu_slope and want_channel_sums."""
+    CIN = FWD = PACK_FWD = DGRAD_PACK_BYTES = REFUSAL = DGRAD_LABEL = INPUT_ACT = None
 
     def __init__(self, name, cin, cout, k, act=L.ACT_TANH):
-        if cin != 256 or cout != 3 or k != 9:
-            raise NotImplementedError("the bf16 final convolution is instantiated for 9x9, 256 -> 3 channels")
+        if cin != self.CIN or cout != 3 or k != 9:
+            raise NotImplementedError(self.REFUSAL)
         super().__init__(name, cin, cout, k, 1, "same", act)
         self._pk = PackedOperand(self._pack, self)
 
     def _pack(self, out):
         rt, w = self.rt, self.ps[self.name + "/kernel"]
-        wf, wd = out or (None, _bytes(rt, 4 * L.FIRST9X9_WFRAG_BYTES))
-        wf = pack_final9x9_bf16(rt, w, wf)
-        L.check(rt.lib.vcg_pack_conv9x9_3ch_bf16(w.data_ptr(), 256, 1, wd.data_ptr(), rt.stream), "vcg_pack_conv9x9_3ch_bf16")      # data gradient
+        wf, wd = out or (None, _bytes(rt, self.DGRAD_PACK_BYTES))
+        wf = self.PACK_FWD(rt, w, wf)
+        L.check(rt.lib.vcg_pack_conv9x9_3ch_bf16(w.data_ptr(), self.CIN, 1, wd.data_ptr(), rt.stream), "vcg_pack_conv9x9_3ch_bf16")      # data gradient
         return wf, wd
 
     def forward(self, x, residual=None, tag=None):
@@ -1301,17 +1292,21 @@ class FinalConv9x9Bf16(Conv2D):
         d = self.desc(n, h, w)
         y = rt.empty(n, 3, h, w)
         with Timed(rt, tag):
-            L.check(rt.lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
-                                                    1 if self.act == L.ACT_TANH else 0, y.data_ptr(), rt.stream), "vcg_conv9x9_to3_bf16_fwd")
+            L.check(getattr(rt.lib, self.FWD)(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
+                                              1 if self.act == L.ACT_TANH else 0, y.data_ptr(), rt.stream), self.FWD)
         return y, (x, y, d)
 
-    def backward(self, ctx, dy, need_dx=True, param_grads=True, which=0, tag=None, input_lrelu_slope=None, want_channel_sums=False):
-        """returns dx as bf16 NHWC; with input_lrelu_slope it is already the gradient in front of the LeakyReLU whose output x is.
-        want_channel_sums: returns (dx, (records, count)) -- per-channel sums of dx out of the kernel's epilogue (the producing layer's
-        bias gradient, ConvT3x3Bf16.backward)"""
+    def backward(self, ctx, dy, need_dx=True, param_grads=True, which=0, dx_residual=None, tag=None, input_lrelu_slope=None, want_channel_sums=False):
+        """dy fp32 NCHW; returns dx as bf16 NHWC; with input_lrelu_slope it is already the gradient in front of the LeakyReLU whose output
+        x is.  want_channel_sums: returns (dx, (records, count)) -- per-channel sums of dx out of the kernel's epilogue (the producing
+        layer's bias gradient, ConvT3x3Bf16.backward)"""
         rt = self.rt
         x, y, d = ctx
         n = d.n
+        if dx_residual is not None:
+            raise NotImplementedError("%s[%s]: no gradient joins at the head's input" % (type(self).__name__, self.name))
+        if (input_lrelu_slope is not None or want_channel_sums) and not self.INPUT_ACT:
+            raise NotImplementedError("%s[%s]: no activation mask or channel sums in the data gradient" % (type(self).__name__, self.name))
         db_done = self.act != L.ACT_NONE
         if db_done:
             dy = act_bwd_bias(self, y, dy, d, param_grads, which)
@@ -1332,21 +1327,33 @@ class FinalConv9x9Bf16(Conv2D):
             return None
         _, wd = self._pk.get()
         dx = torch.empty_like(x)
+        mask = x.data_ptr() if input_lrelu_slope is not None else None
         if want_channel_sums:
             nrec = rt.lib.vcg_conv9x9_to3_bf16_dgrad_chsum_records(ctypes.byref(d))
             L.check(min(nrec, 0), "vcg_conv9x9_to3_bf16_dgrad_chsum_records")
             rec = rt.empty(nrec * self.cin)
             with Timed(rt, tag and tag + "_dgrad"):
-                L.check(rt.lib.vcg_conv9x9_to3_bf16_dgrad_chsum(ctypes.byref(d), dy.data_ptr(), wd.data_ptr(),
-                                                                x.data_ptr() if input_lrelu_slope is not None else None,
-                                                                float(input_lrelu_slope or 0.0), dx.data_ptr(), rec.data_ptr(), rt.stream),
-                        "vcg_conv9x9_to3_bf16_dgrad_chsum")
+                L.check(rt.lib.vcg_conv9x9_to3_bf16_dgrad_chsum(ctypes.byref(d), dy.data_ptr(), wd.data_ptr(), mask, float(input_lrelu_slope or 0.0),
+                                                                dx.data_ptr(), rec.data_ptr(), rt.stream), "vcg_conv9x9_to3_bf16_dgrad_chsum")
             return dx, (rec, nrec)
         with Timed(rt, tag and tag + "_dgrad"):
-            L.check(rt.lib.vcg_conv9x9_to3_bf16_dgrad(ctypes.byref(d), dy.data_ptr(), wd.data_ptr(),
-                                                      x.data_ptr() if input_lrelu_slope is not None else None,
-                                                      float(input_lrelu_slope or 0.0), dx.data_ptr(), rt.stream), "vcg_conv9x9_to3_bf16_dgrad")
+            L.check(rt.lib.vcg_conv9x9_to3_bf16_dgrad(ctypes.byref(d), dy.data_ptr(), wd.data_ptr(), mask, float(input_lrelu_slope or 0.0),
+                                                      dx.data_ptr(), rt.stream), self.DGRAD_LABEL % {"name": self.name})
         return dx
+
+
+class FinalConv9x9Bf16(Conv9x9To3Bf16):
+    """final/conv (model.py:290-291) behind the 256-channel up-sampling stage; its data gradient also applies the derivative of the
+    LeakyReLU that produced the input and can leave the per-channel sums of the result"""
+    CIN, FWD, PACK_FWD, DGRAD_PACK_BYTES, INPUT_ACT = 256, "vcg_conv9x9_to3_bf16_fwd", staticmethod(pack_final9x9_bf16), 4 * L.FIRST9X9_WFRAG_BYTES, True
+    REFUSAL, DGRAD_LABEL = "the bf16 final convolution is instantiated for 9x9, 256 -> 3 channels", "vcg_conv9x9_to3_bf16_dgrad"
+
+
+class HeadConv9x9C64Bf16(Conv9x9To3Bf16):
+    """head/conv of make_generator_cyclegan behind the last 64-channel up-sampling stage, which has no activation of its own"""
+    CIN, FWD, PACK_FWD, DGRAD_PACK_BYTES, INPUT_ACT = 64, "vcg_conv9x9_c64to3_bf16_fwd", staticmethod(pack_conv9x9_c64to3_bf16), L.FIRST9X9_WFRAG_BYTES, False
+    REFUSAL, DGRAD_LABEL = "the bf16 head convolution is instantiated for 9x9, 64 -> 3 channels", "vcg_conv9x9_to3_bf16_dgrad[%(name)s]"
+
 
 
 class StemConv9x9Bf16(InitialConv9x9Bf16):
@@ -1370,83 +1377,12 @@ class StemConv9x9Bf16(InitialConv9x9Bf16):
         return z, ctx, None
 
     def backward(self, ctx, dz, need_dx=True, param_grads=True, which=0, dx_residual=None, tag=None):
-        rt, lib = self.rt, self.rt.lib
         x, _, d = ctx
         if need_dx:
             raise NotImplementedError("StemConv9x9Bf16[%s] reads the network input: no data gradient" % self.name)
-        if not param_grads:
-            return None
-        need = lib.vcg_conv3ch_bf16_wgrad_workspace_bytes(ctypes.byref(d))
-        if need:
-            ws, wsn = rt.workspace(need)
-            with Timed(rt, tag and tag + "_wgrad"):
-                L.check(lib.vcg_conv3ch_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dz.data_ptr(), self.ps.grad(self.name + "/kernel", which).data_ptr(),
-                                                   self.ps.grad(self.name + "/bias", which).data_ptr(), ws, wsn, rt.stream),
-                        "vcg_conv3ch_bf16_wgrad[%s]" % self.name)
-        else:       # odd widths
-            self._wgrad_fp32(d, x, from_bf16_nhwc(rt, dz), which, True, tag)
+        if param_grads:
+            conv3ch_bf16_wgrad(self, d, x, dz, which, tag)
         return None
-
-
-class HeadConv9x9C64Bf16(Conv2D):
-    """head/conv of make_generator_cyclegan: Conv2D(3, 9, 'same') + tanh on a bf16 NHWC input with 64 channels, fp32 NCHW output -- the
-    64-channel counterpart of FinalConv9x9Bf16.  Forward on vcg_conv9x9_c64to3_bf16_fwd; data gradient on vcg_conv9x9_to3_bf16_dgrad with
-    the kernel packed by vcg_pack_conv9x9_3ch_bf16(w, 64, 1) (the 3 -> 64 kernel of the stem with the roles swapped); weight gradient on
-    vcg_conv9x9_to3_bf16_wgrad at cin = 64 (even widths; odd ones take the fp32 kernel on an fp32 NCHW copy of the input)."""
-
-    def __init__(self, name, cin, cout, k, act=L.ACT_TANH):
-        if cin != 64 or cout != 3 or k != 9:
-            raise NotImplementedError("the bf16 head convolution is instantiated for 9x9, 64 -> 3 channels")
-        super().__init__(name, cin, cout, k, 1, "same", act)
-        self._pk = PackedOperand(self._pack, self)
-
-    def _pack(self, out):
-        rt, w = self.rt, self.ps[self.name + "/kernel"]
-        wf, wd = out or (None, _bytes(rt, L.FIRST9X9_WFRAG_BYTES))
-        wf = pack_conv9x9_c64to3_bf16(rt, w, wf)
-        L.check(rt.lib.vcg_pack_conv9x9_3ch_bf16(w.data_ptr(), 64, 1, wd.data_ptr(), rt.stream), "vcg_pack_conv9x9_3ch_bf16")      # data gradient
-        return wf, wd
-
-    def forward(self, x, residual=None, tag=None):
-        rt = self.rt
-        n, h, w, _ = x.shape
-        wf, _ = self._pk.get()
-        d = self.desc(n, h, w)
-        y = rt.empty(n, 3, h, w)
-        with Timed(rt, tag):
-            L.check(rt.lib.vcg_conv9x9_c64to3_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
-                                                       1 if self.act == L.ACT_TANH else 0, y.data_ptr(), rt.stream), "vcg_conv9x9_c64to3_bf16_fwd")
-        return y, (x, y, d)
-
-    def backward(self, ctx, dy, need_dx=True, param_grads=True, which=0, dx_residual=None, tag=None):
-        """dy fp32 NCHW; returns dx as bf16 NHWC"""
-        rt = self.rt
-        x, y, d = ctx
-        if dx_residual is not None:
-            raise NotImplementedError("HeadConv9x9C64Bf16[%s]: no gradient joins at the head's input" % self.name)
-        db_done = self.act != L.ACT_NONE
-        if db_done:
-            dy = act_bwd_bias(self, y, dy, d, param_grads, which)
-        if param_grads and d.w % 2 == 0:
-            ws, wsn = rt.workspace(max(rt.lib.vcg_conv9x9_to3_bf16_wgrad_workspace_bytes(ctypes.byref(d)),
-                                       rt.lib.vcg_channel_sum_workspace_bytes(d.n, 3, d.oh * d.ow)))
-            with Timed(rt, tag and tag + "_wgrad"):
-                L.check(rt.lib.vcg_conv9x9_to3_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dy.data_ptr(), self.ps.grad(self.name + "/kernel", which).data_ptr(),
-                                                          ws, wsn, rt.stream), "vcg_conv9x9_to3_bf16_wgrad[%s]" % self.name)
-            if not db_done:
-                L.check(rt.lib.vcg_channel_sum(dy.data_ptr(), d.n, 3, d.oh * d.ow, self.ps.grad(self.name + "/bias", which).data_ptr(), ws, wsn,
-                                               rt.stream), "vcg_channel_sum[%s]" % self.name)
-        elif param_grads:
-            # odd widths: the fp32 kernel on an fp32 NCHW copy of the input (exact conversion)
-            self._wgrad_fp32(d, from_bf16_nhwc(rt, x), dy, which, not db_done, tag)
-        if not need_dx:
-            return None
-        _, wd = self._pk.get()
-        dx = torch.empty_like(x)
-        with Timed(rt, tag and tag + "_dgrad"):
-            L.check(rt.lib.vcg_conv9x9_to3_bf16_dgrad(ctypes.byref(d), dy.data_ptr(), wd.data_ptr(), None, 0.0, dx.data_ptr(), rt.stream),
-                    "vcg_conv9x9_to3_bf16_dgrad[%s]" % self.name)
-        return dx
 
 
 class NormActBf16(NormAct):

@@ -280,56 +280,101 @@ class Bf16Generator:
     def _conv_instance_norm(self, x, w, y, bias, act, alpha, res, n, h, wd):
         """conv (+bias) -> per-image statistics -> normalise + activation + Add, all on bf16 NHWC"""
         rt = self.rt
-        z = self._trunk_buffers(n, h, wd)["z"]
+        B = self._trunk_buffers(n, h, wd)
         k = self.k
         d = L.ConvDesc(n, 64, h, wd, 64, h, wd, k, k, 1, k // 2, k // 2)
         ep = L.EpilogueBf16(None, bias.data_ptr(), L.ACT_NONE, 0.0, None, None)
-        L.check(rt.lib.vcg_conv2d_bf16_fwd(ctypes.byref(d), x.data_ptr(), w.data_ptr(), z.data_ptr(), ctypes.byref(ep), rt.stream),
+        L.check(rt.lib.vcg_conv2d_bf16_fwd(ctypes.byref(d), x.data_ptr(), w.data_ptr(), B["z"].data_ptr(), ctypes.byref(ep), rt.stream),
                 "vcg_conv2d_bf16_fwd")
-        st = self._trunk_buffers(n, h, wd)["stats"]
-        mean, var, scale, shift, invstd = (st[i] for i in range(5))
-        ws, wsn = rt.workspace(rt.lib.vcg_norm_stats_bf16_workspace_bytes(n, 64, h * wd, L.NORM_INSTANCE))
-        L.check(rt.lib.vcg_norm_stats_bf16(z.data_ptr(), n, 64, h * wd, L.NORM_INSTANCE, mean.data_ptr(), var.data_ptr(), ws, wsn,
-                                           rt.stream), "vcg_norm_stats_bf16")
-        L.check(rt.lib.vcg_norm_finalize(mean.data_ptr(), var.data_ptr(), None, None, 64, n, E.IN_EPS, scale.data_ptr(), shift.data_ptr(),
-                                         invstd.data_ptr(), None, None, 0.0, 0, rt.stream), "vcg_norm_finalize")
-        L.check(rt.lib.vcg_norm_act_fwd_bf16(z.data_ptr(), n, 64, h * wd, scale.data_ptr(), shift.data_ptr(), 1, act, 0.0,
+        self._norm_act(B["z"], y, B["stats"], alpha, res)
+
+    def _norm_act(self, z, y, stats, alpha, res, nrec=-1, part=None, scale=None, shift=None):
+        """the norm (+ PReLU with the slopes alpha, + Add of res) behind a convolution, z -> y on bf16 NHWC.  stats: instance norm's
+        [5, >= n * c] scratch -- the per-image scale / shift come from the convolution's epilogue records part (nrec > 0 per image:
+        vcg_norm_finalize_partials) or from a statistics pass over z; None: the per-channel scale / shift given"""
+        rt = self.rt
+        n, h, w, c = z.shape
+        if stats is not None:
+            mean, var, scale, shift, invstd = (stats[i] for i in range(5))
+            if nrec > 0:
+                L.check(rt.lib.vcg_norm_finalize_partials(part.data_ptr(), nrec, n, c, float(h * w), None, None, E.IN_EPS, mean.data_ptr(),
+                                                          scale.data_ptr(), shift.data_ptr(), invstd.data_ptr(), None, None, 0.0, 0, rt.stream),
+                        "vcg_norm_finalize_partials")
+            else:
+                ws, wsn = rt.workspace(rt.lib.vcg_norm_stats_bf16_workspace_bytes(n, c, h * w, L.NORM_INSTANCE))
+                L.check(rt.lib.vcg_norm_stats_bf16(z.data_ptr(), n, c, h * w, L.NORM_INSTANCE, mean.data_ptr(), var.data_ptr(), ws, wsn,
+                                                   rt.stream), "vcg_norm_stats_bf16")
+                L.check(rt.lib.vcg_norm_finalize(mean.data_ptr(), var.data_ptr(), None, None, c, n, E.IN_EPS, scale.data_ptr(), shift.data_ptr(),
+                                                 invstd.data_ptr(), None, None, 0.0, 0, rt.stream), "vcg_norm_finalize")
+        L.check(rt.lib.vcg_norm_act_fwd_bf16(z.data_ptr(), n, c, h * w, scale.data_ptr(), shift.data_ptr(), 1 if stats is not None else 0,
+                                             L.ACT_PRELU if alpha is not None else L.ACT_NONE, 0.0,
                                              alpha.data_ptr() if alpha is not None else None,
                                              res.data_ptr() if res is not None else None, y.data_ptr(), rt.stream),
                 "vcg_norm_act_fwd_bf16")
 
-    def forward(self, x, out_kind=L.OUT_F32_NCHW, band_rows=None):
-        """x: device fp32 NCHW [n,3,h,w] in [-1,1] -> device fp32 NCHW [n,3,f*h,f*w], or with out_kind OUT_U8_NHWC device uint8 frames
-        [n,f*h,f*w,3] (f = upscale_factor; buffer owned by the engine).  band_rows: see tail_plan"""
+    def _stem(self, x, w, bias, alpha, y):
+        """the 9x9 3 -> 64 convolution of the fp32 NCHW frames x + bias (+ PReLU with the slopes alpha, or None) -> y bf16 NHWC"""
         rt = self.rt
+        n, _, h, wd = x.shape
+        d = L.ConvDesc(n, 3, h, wd, 64, h, wd, 9, 9, 1, 4, 4)
+        L.check(rt.lib.vcg_conv9x9_from3_bf16_fwd(ctypes.byref(d), x.data_ptr(), w.data_ptr(), bias.data_ptr(),
+                                                  alpha.data_ptr() if alpha is not None else None, y.data_ptr(), rt.stream),
+                "vcg_conv9x9_from3_bf16_fwd")
+
+    def _trunk(self, x, B, gate=None):
+        """initial/conv, the residual blocks and the convolution behind them (+ long skip) on the buffers B; returns the buffer that holds
+        the result.  gate(block's gate weights, block input, B["g"]): the attention engine's gate in front of a block's first convolution"""
         n, _, h, w = x.shape
-        ch, bands = self._plan(n, h, w, band_rows, out_kind)
-        banded = len(bands) > 1 or out_kind != L.OUT_F32_NCHW
-        B = self._trunk_buffers(n, h, w) if banded else self._buffers(n, h, w)
-        w0, b0, a0 = self.first
-        d0 = L.ConvDesc(n, 3, h, w, 64, h, w, 9, 9, 1, 4, 4)
-        L.check(rt.lib.vcg_conv9x9_from3_bf16_fwd(ctypes.byref(d0), x.data_ptr(), w0.data_ptr(), b0.data_ptr(), a0.data_ptr(),
-                                                  B["skip"].data_ptr(), rt.stream), "vcg_conv9x9_from3_bf16_fwd")
+        self._stem(x, *self.first, B["skip"])
         cur = B["skip"]                     # block input; outputs ping-pong between "a" and "c", "skip" is never overwritten
-        for (w1, s1, h1, al, w2, s2, h2) in self.trunk:
+        for blk in self.trunk:
+            w1, s1, h1, al, w2, s2, h2 = blk[-7:]
             out = B["a"] if cur is not B["a"] else B["c"]
-            self._conv(cur, w1, B["b"], s1, h1, L.ACT_PRELU, al, None, n, h, w)
-            self._conv(B["b"], w2, out, s2, h2, L.ACT_NONE, None, cur, n, h, w)
+            src = cur
+            if gate is not None:
+                gate(blk[0], cur, B["g"])
+                src = B["g"]
+            self._conv(src, w1, B["b"], s1, h1, L.ACT_PRELU, al, None, n, h, w)
+            self._conv(B["b"], w2, out, s2, h2, L.ACT_NONE, None, cur, n, h, w)          # Add of the (ungated) block input
             cur = out
         wp, sp, hp = self.prefinal
         out = B["a"] if cur is not B["a"] else B["c"]
         self._conv(cur, wp, out, sp, hp, L.ACT_NONE, None, B["skip"], n, h, w)
+        return out
+
+    def _to3(self, src, y, out_kind=L.OUT_F32_NCHW, window=None):
+        """the last convolution, Conv2D(3, 9, 'same') + tanh with self.final's packed kernel and bias, of the bf16 NHWC tensor src into
+        the frames y (its first y.shape[0] images): the 64-channel entry point or the one that takes the channel count; the plain form
+        for fp32 output of whole frames, the window form for uint8 output (the whole frame as one window) or for a given window =
+        (row0, rows, y_row0, frame_rows)"""
+        rt = self.rt
+        wf, bias = self.final[:2]
+        _, hh, ww, cin = src.shape
+        d = L.ConvDesc(y.shape[0], cin, hh, ww, 3, hh, ww, 9, 9, 1, 4, 4)
+        name = "vcg_conv9x9_c64to3_bf16_fwd" if cin == 64 else "vcg_conv9x9_to3_bf16_fwd"
+        if window is None and out_kind == L.OUT_F32_NCHW:
+            L.check(getattr(rt.lib, name)(ctypes.byref(d), src.data_ptr(), wf.data_ptr(), bias.data_ptr(), 1, y.data_ptr(), rt.stream), name)
+        else:
+            row0, rows, y_row0, frame_rows = window or (0, hh, 0, hh)
+            L.check(getattr(rt.lib, name + "_window")(ctypes.byref(d), src.data_ptr(), wf.data_ptr(), bias.data_ptr(), 1, out_kind, y.data_ptr(),
+                                                      row0, rows, y_row0, frame_rows, rt.stream), name + "_window")
+
+    def forward(self, x, out_kind=L.OUT_F32_NCHW, band_rows=None):
+        """x: device fp32 NCHW [n,3,h,w] in [-1,1] -> device fp32 NCHW [n,3,f*h,f*w], or with out_kind OUT_U8_NHWC device uint8 frames
+        [n,f*h,f*w,3] (f = upscale_factor; buffer owned by the engine).  band_rows: see tail_plan"""
+        n, _, h, w = x.shape
+        ch, bands = self._plan(n, h, w, band_rows, out_kind)
+        banded = len(bands) > 1 or out_kind != L.OUT_F32_NCHW
+        B = self._trunk_buffers(n, h, w) if banded else self._buffers(n, h, w)
+        out = self._trunk(x, B)
         if banded:
             return self._tail_bands(out, n, h, w, ch, bands, out_kind)
-        wf, bf_ = self.final
         us, y = B["us"], B["y"]
         ch = us[0].shape[0]
         for i in range(0, n, ch):
             c = min(ch, n - i)
             src, hh, ww = self._upsample(out[i:i + c], us, c, h, w)
-            df = L.ConvDesc(c, 256, hh, ww, 3, hh, ww, 9, 9, 1, 4, 4)
-            L.check(rt.lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, y[i:i + c].data_ptr(),
-                                                    rt.stream), "vcg_conv9x9_to3_bf16_fwd")
+            self._to3(src, y[i:i + c])
         return B["y"]
 
     def _upsample(self, src, us, c, hh, ww):
@@ -351,9 +396,7 @@ class Bf16Generator:
     def _tail_bands(self, out, n, h, w, ch, bands, out_kind):
         """the tail band by band: the band's rows of the trunk output in a compact buffer (a strided copy: 64 channels at low resolution),
         the up-sampling stages unchanged on the band, final/conv on the band's window into its rows of the frames"""
-        rt = self.rt
         T = self._band_buffers(n, h, w, ch, bands, out_kind)
-        wf, bf_ = self.final
         f, y = 2 ** len(self.ups), T["y"]
         for i in range(0, n, ch):
             c = min(ch, n - i)
@@ -366,10 +409,7 @@ class Bf16Generator:
                     src.copy_(out[i:i + c, b.start:b.end])
                 us = [u[:c * 4 ** (s + 1) * rows * w * 256].view(c, 2 ** (s + 1) * rows, 2 ** (s + 1) * w, 256) for s, u in enumerate(T["us"])]
                 src, hh, ww = self._upsample(src, us, c, rows, w)
-                df = L.ConvDesc(c, 256, hh, ww, 3, hh, ww, 9, 9, 1, 4, 4)
-                L.check(rt.lib.vcg_conv9x9_to3_bf16_fwd_window(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, out_kind,
-                                                               y[i:i + c].data_ptr(), b.row0, b.rows, b.y_row0, f * h, rt.stream),
-                        "vcg_conv9x9_to3_bf16_fwd_window")
+                self._to3(src, y[i:i + c], out_kind, (b.row0, b.rows, b.y_row0, f * h))
         return y
 
     # ---- hipGraph ---------------------------------------------------------------------------------------------
@@ -600,20 +640,7 @@ class Bf16AttentionGenerator(Bf16Generator):
         n, _, h, w = x.shape
         self._plan(n, h, w, band_rows, out_kind)          # refuses what the tail does not serve
         B = self._buffers(n, h, w)
-        w0, b0, a0 = self.first
-        d0 = L.ConvDesc(n, 3, h, w, 64, h, w, 9, 9, 1, 4, 4)
-        L.check(rt.lib.vcg_conv9x9_from3_bf16_fwd(ctypes.byref(d0), x.data_ptr(), w0.data_ptr(), b0.data_ptr(), a0.data_ptr(),
-                                                  B["skip"].data_ptr(), rt.stream), "vcg_conv9x9_from3_bf16_fwd")
-        cur = B["skip"]                     # block input; outputs ping-pong between "a" and "c", "skip" is never overwritten
-        for (gate, w1, s1, h1, al, w2, s2, h2) in self.trunk:
-            out = B["a"] if cur is not B["a"] else B["c"]
-            self._gate(gate, x, 3, cur, B["g"], n, h, w)
-            self._conv(B["g"], w1, B["b"], s1, h1, L.ACT_PRELU, al, None, n, h, w)
-            self._conv(B["b"], w2, out, s2, h2, L.ACT_NONE, None, cur, n, h, w)          # Add of the ungated block input
-            cur = out
-        wp, sp, hp = self.prefinal
-        out = B["a"] if cur is not B["a"] else B["c"]
-        self._conv(cur, wp, out, sp, hp, L.ACT_NONE, None, B["skip"], n, h, w)
+        out = self._trunk(x, B, lambda gate, m, g: self._gate(gate, x, 3, m, g, n, h, w))
         # the gates' inputs: data derived from the frames alone, for the whole batch
         for s, st in enumerate(B["stages"]):
             r, hw = 2 ** s, h * w
@@ -623,7 +650,6 @@ class Bf16AttentionGenerator(Bf16Generator):
                     L.check(rt.lib.vcg_resize2d(x.data_ptr(), st["t"].data_ptr(), n * 3, h, w, r, bil, rt.stream), "vcg_resize2d")
                     src = st["t"]
                 L.check(rt.lib.vcg_copy_channels(src.data_ptr(), st["u"].data_ptr(), n, 3, 0, 6, off, 3, r * r * hw, rt.stream), "vcg_copy_channels")
-        wf, bf_, cfin = self.final
         k, crop = self.k, max(self.k - 2, 0) // 2           # TF-SAME crop of Conv2DTranspose(k, strides 2): k3 (0, 1), k5 (1, 2)
         ch, f = B["chunk"], 2 ** len(self.ups)
         if out_kind == L.OUT_U8_NHWC:
@@ -645,13 +671,7 @@ class Bf16AttentionGenerator(Bf16Generator):
                 L.check(rt.lib.vcg_input_convt_add_bf16(ctypes.byref(da), x[i:i + c].data_ptr(), wa.data_ptr(), ba.data_ptr(), st["y"].data_ptr(),
                                                         rt.stream), "vcg_input_convt_add_bf16")
                 src, hh, ww = st["y"], 2 * hh, 2 * ww
-            df = L.ConvDesc(c, cfin, hh, ww, 3, hh, ww, 9, 9, 1, 4, 4)
-            if out_kind == L.OUT_U8_NHWC:             # the whole frame as one window: final/conv stores the uint8 NHWC frames
-                L.check(rt.lib.vcg_conv9x9_to3_bf16_fwd_window(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, out_kind,
-                                                               y[i:i + c].data_ptr(), 0, hh, 0, hh, rt.stream), "vcg_conv9x9_to3_bf16_fwd_window")
-            else:
-                L.check(rt.lib.vcg_conv9x9_to3_bf16_fwd(ctypes.byref(df), src.data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, y[i:i + c].data_ptr(),
-                                                        rt.stream), "vcg_conv9x9_to3_bf16_fwd")
+            self._to3(src, y[i:i + c], out_kind)       # uint8: the whole frame as one window, final/conv stores the uint8 NHWC frames
         return y
 
 
@@ -823,37 +843,15 @@ class Bf16CycleGanGenerator(Bf16Generator):
     # ---- one forward pass --------------------------------------------------------------------------------------
     def _norm(self, P, s):
         """the norm (+ PReLU, + Add) behind a convolution: z -> y"""
-        rt, op, c = self.rt, s["op"], s["z"].shape[0]
-        z, co, hw = s["z"], s["c"], s["hw"]
-        if self.instance:
-            mean, var, scale, shift, invstd = (P["stats"][i] for i in range(5))
-            if s["nrec"] > 0:
-                L.check(rt.lib.vcg_norm_finalize_partials(P["part"].data_ptr(), s["nrec"], c, co, float(hw), None, None, E.IN_EPS,
-                                                          mean.data_ptr(), scale.data_ptr(), shift.data_ptr(), invstd.data_ptr(), None, None,
-                                                          0.0, 0, rt.stream), "vcg_norm_finalize_partials")
-            else:
-                ws, wsn = rt.workspace(rt.lib.vcg_norm_stats_bf16_workspace_bytes(c, co, hw, L.NORM_INSTANCE))
-                L.check(rt.lib.vcg_norm_stats_bf16(z.data_ptr(), c, co, hw, L.NORM_INSTANCE, mean.data_ptr(), var.data_ptr(), ws, wsn,
-                                                   rt.stream), "vcg_norm_stats_bf16")
-                L.check(rt.lib.vcg_norm_finalize(mean.data_ptr(), var.data_ptr(), None, None, co, c, E.IN_EPS, scale.data_ptr(),
-                                                 shift.data_ptr(), invstd.data_ptr(), None, None, 0.0, 0, rt.stream), "vcg_norm_finalize")
-            per_sample = 1
-        else:
-            scale, shift, per_sample = op["scale"], op["shift"], 0
-        alpha = op["alpha"]
-        L.check(rt.lib.vcg_norm_act_fwd_bf16(z.data_ptr(), c, co, hw, scale.data_ptr(), shift.data_ptr(), per_sample,
-                                             L.ACT_PRELU if alpha is not None else L.ACT_NONE, 0.0,
-                                             alpha.data_ptr() if alpha is not None else None,
-                                             s["res"].data_ptr() if s["res"] is not None else None, s["y"].data_ptr(), rt.stream),
-                "vcg_norm_act_fwd_bf16")
+        op = s["op"]
+        self._norm_act(s["z"], s["y"], P["stats"], op["alpha"], s["res"], s["nrec"], P["part"], op["scale"], op["shift"])
 
     def _conv_step(self, P, s, x):
         """the convolution (+ bias) of one step: its input (the frames x for the stem) -> z, with the statistics records where planned"""
         rt = self.rt
         op, d, z = s["op"], s["d"], s["z"]
         if op["kind"] == "stem":
-            L.check(rt.lib.vcg_conv9x9_from3_bf16_fwd(ctypes.byref(d), x.data_ptr(), op["w"].data_ptr(), op["bias"].data_ptr(), None,
-                                                      z.data_ptr(), rt.stream), "vcg_conv9x9_from3_bf16_fwd")
+            self._stem(x, op["w"], op["bias"], None, z)
         elif op["kind"] == "convt":
             L.check(rt.lib.vcg_conv_transpose2d_nhwc_bf16_fwd(ctypes.byref(d), s["x"].data_ptr(), op["w"].data_ptr(), op["bias"].data_ptr(),
                                                               L.ACT_NONE, 0.0, z.data_ptr(), rt.stream), "vcg_conv_transpose2d_nhwc_bf16_fwd")
@@ -866,7 +864,6 @@ class Bf16CycleGanGenerator(Bf16Generator):
 
     def _pass(self, x, y, out_kind, taps):
         """the pass on one chunk: x fp32 NCHW [c,3,h,w] -> y (its frames of the output buffer)"""
-        rt = self.rt
         c, _, h, w = x.shape
         P = self._launches(c, h, w)
 
@@ -879,15 +876,7 @@ class Bf16CycleGanGenerator(Bf16Generator):
             tap(s["op"]["conv"], s["z"])
             self._norm(P, s)
             tap(s["op"]["out"], s["y"])
-        wf, bf_ = self.final
-        f = self._factor()
-        df = L.ConvDesc(c, 64, f * h, f * w, 3, f * h, f * w, 9, 9, 1, 4, 4)
-        if out_kind == L.OUT_U8_NHWC:             # the whole frame as one window: head/conv stores the uint8 NHWC frames
-            L.check(rt.lib.vcg_conv9x9_c64to3_bf16_fwd_window(ctypes.byref(df), P["last"].data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, out_kind,
-                                                              y.data_ptr(), 0, f * h, 0, f * h, rt.stream), "vcg_conv9x9_c64to3_bf16_fwd_window")
-        else:
-            L.check(rt.lib.vcg_conv9x9_c64to3_bf16_fwd(ctypes.byref(df), P["last"].data_ptr(), wf.data_ptr(), bf_.data_ptr(), 1, y.data_ptr(),
-                                                       rt.stream), "vcg_conv9x9_c64to3_bf16_fwd")
+        self._to3(P["last"], y, out_kind)           # uint8: the whole frame as one window, head/conv stores the uint8 NHWC frames
         tap("head/conv", y)
 
     def forward(self, x, out_kind=L.OUT_F32_NCHW, band_rows=None, taps=None):
