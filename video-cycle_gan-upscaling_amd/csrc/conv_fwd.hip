@@ -332,6 +332,8 @@ __global__ __launch_bounds__(256, (KH >= 9 ? 1 : 2)) void conv_fwd_kernel(const 
 // matrix work on zeros).  Here the whole (channel, ky, kx) range is one flat K axis staged once, and an MFMA
 // takes two CONSECUTIVE k: the second half-wave reads one element further along the tap row, with the two
 // row / channel wrap-arounds handled by two more per-lane base pointers chosen at compile time.
+// A tile has few MFMAs (9x9: 488 a wave) against a 62.5 KB weight slab, so the kernel is persistent: a workgroup
+// keeps its 64-channel block's weights in LDS and walks spatial tiles, the input tile double-buffered.
 // ------------------------------------------------------------------------------------------------
 template <int KH, int KW, int S>
 struct C3Cfg {
@@ -347,7 +349,11 @@ struct C3Cfg {
     static constexpr int W_ELEMS = W_ROWS * 64;
     static constexpr int IN_PT = (IN_ELEMS + 255) / 256;
     static constexpr int W_PT = W_ELEMS / 256;
-    static constexpr size_t LDS_BYTES = (size_t)(IN_ELEMS + W_ELEMS) * sizeof(float);
+    // one input buffer: the halo tile and four zero words.  When KT is odd the second half-wave's read behind the last k
+    // lands on the first of them (its weight row is zero, but 0 * NaN is NaN: the word has to be finite)
+    static constexpr int IN_BUF = IN_ELEMS + 4;
+    static constexpr size_t LDS_BYTES = (size_t)(2 * IN_BUF + W_ELEMS) * sizeof(float);
+    static_assert(IW < 256 && W_ELEMS % 256 == 0, "packed (row, column) of a halo element; whole weight rows per wave");
     static constexpr int off(int k) { return (k / T) * PLANE + ((k % T) / KW) * IW + (k % T) % KW; }
     static constexpr int D_ROW = IW - (KW - 1);                              // kx wraps to the next tap row
     static constexpr int D_CH = PLANE - (KH - 1) * IW - (KW - 1);            // last tap -> first tap of next channel
@@ -357,75 +363,161 @@ template <int KH, int KW, int S>
 __global__ __launch_bounds__(256, 2) void conv_c3_kernel(const ConvParams p) {
     using C = C3Cfg<KH, KW, S>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* s_in = smem;               // [3][IH][IW]
-    float* s_w = smem + C::IN_ELEMS;  // [W_ROWS][64]
+    float* s_in = smem;                   // [2][IN_BUF]: halo tile [3][IH][IW] + zero words, double-buffered
+    float* s_w = smem + 2 * C::IN_BUF;    // [W_ROWS][64]
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
-    int b = blockIdx.x;
-    const int cb = b % p.co_blocks; b /= p.co_blocks;
-    const int tx = b % p.tiles_x;   b /= p.tiles_x;
-    const int ty = b % p.tiles_y;   b /= p.tiles_y;
-    const int n = b;
-    const int ox0 = tx * 32, oy0 = ty * C::ROWS, co0 = cb * 64;
-    const int gy0 = oy0 * S - p.pad_top, gx0 = ox0 * S - p.pad_left;
-    const float* xn = p.x + (size_t)n * p.cin * p.h * p.w_;
+    // persistent: the workgroup keeps one 64-channel block, whose weights it stages once, and walks the spatial tiles
+    // t, t + step, ... in (image, tile_y, tile_x) order; the coordinates are carried from tile to tile
+    const int nblk = p.co_blocks, step = (int)gridDim.x / nblk;
+    const int cb = (int)blockIdx.x % nblk, co0 = cb * 64;
+    int t = (int)blockIdx.x / nblk;
+    const int tiles = p.n * p.tiles_y * p.tiles_x;
+    if (t >= tiles) return;
+    int tx = t % p.tiles_x, ty = (t / p.tiles_x) % p.tiles_y, n = t / (p.tiles_x * p.tiles_y);
+    const int dtx = step % p.tiles_x, dty = (step / p.tiles_x) % p.tiles_y, dn = step / (p.tiles_x * p.tiles_y);
 
-    // ---- stage everything once: input halo tile of all channels + the whole weight slab of this block
+    // ---- the thread's halo elements e = tid + 256 i: byte offset from the tile's first element and packed (row, column).
+    // Decoded once per kernel where that costs at most 16 registers; the stride-2 tile (14 elements a thread) decodes
+    // per tile, as every workgroup did before: held there, hipcc spills
+    constexpr bool KEEP = C::IN_PT <= 8;
+    const int hw = p.h * p.w_;
+    const unsigned w4 = 4u * (unsigned)p.w_, hw4 = 4u * (unsigned)hw;
+    const size_t img_bytes = (size_t)p.cin * hw * sizeof(float);
+    auto decode = [&](int tid_, int i, unsigned& rel_, unsigned& rc_) {
+        const int e = tid_ + i * 256;
+        const int ci = e / C::PLANE, rem = e % C::PLANE;
+        const int r = rem / C::IW, c = rem % C::IW;
+        rel_ = (unsigned)ci * hw4 + (unsigned)r * w4 + 4u * (unsigned)c;
+        rc_ = (unsigned)(r << 8 | c);
+    };
+    unsigned rel[KEEP ? C::IN_PT : 1], rc[KEEP ? C::IN_PT : 1];
+    if constexpr (KEEP) {
 #pragma unroll
-    for (int i = 0; i < C::IN_PT; ++i) {
-        const int e = tid + i * 256;
-        if (e < C::IN_ELEMS) {
-            const int ci = e / C::PLANE, rem = e % C::PLANE;
-            const int r = rem / C::IW, c = rem % C::IW;
-            const int gy = gy0 + r, gx = gx0 + c;
-            const bool ok = ci < p.cin && gy >= 0 && gy < p.h && gx >= 0 && gx < p.w_;
-            const float v = xn[ok ? (ci * p.h + gy) * p.w_ + gx : 0];
-            s_in[e] = ok ? v : 0.f;
+        for (int i = 0; i < C::IN_PT; ++i) {
+            decode(tid, i, rel[i], rc[i]);
+            asm volatile("" : "+v"(rc[i]));            // one register: hipcc would carry row and column apart
         }
     }
-#pragma unroll 4
-    for (int i = 0; i < C::W_PT; ++i) {
-        const int e = tid + i * 256;
-        const int m = e & 63, k = e >> 6;              // k = ci*T + tap
-        const int ci = k / C::T, t = k % C::T;
-        const int tap = p.flip ? (C::T - 1 - t) : t;
-        const bool ok = k < C::KT && ci < p.cin && co0 + m < p.cout;
-        const float v = p.w[ok ? (tap * p.cin + ci) * p.cout + co0 + m : 0];
-        s_w[e] = ok ? v : 0.f;
+    const bool last_live = tid + (C::IN_PT - 1) * 256 < C::IN_ELEMS;   // only the last element can lie past the tile
+    // a tile's loads: one select per element, on the offset.  Padding and the ragged edge get VCG_OOB and read 0; a
+    // channel past cin lies behind the image's records on its own (conv_block_fits keeps 3 planes below 4 GiB)
+    float rin[C::IN_PT];
+    auto load_tile = [&](int n_, int ty_, int tx_) {
+        const int gy0 = ty_ * C::ROWS * S - p.pad_top, gx0 = tx_ * 32 * S - p.pad_left;
+        const vcg_rsrc rx = make_rsrc(p.x + (size_t)n_ * p.cin * hw, img_bytes);
+        const unsigned tb = (unsigned)gy0 * w4 + 4u * (unsigned)gx0;      // modulo 2^32 while outside the map, exact inside
+        int tid_t = tid;
+        if constexpr (!KEEP) asm volatile("" : "+v"(tid_t));             // a decode per tile stays one: not hoisted out of the tile loop
+#pragma unroll
+        for (int i = 0; i < C::IN_PT; ++i) {
+            unsigned rl, q;
+            if constexpr (KEEP) { rl = rel[i]; q = rc[i]; } else decode(tid_t, i, rl, q);
+            bool ok = (unsigned)(gy0 + (int)(q >> 8)) < (unsigned)p.h && (unsigned)(gx0 + (int)(q & 255u)) < (unsigned)p.w_;
+            if (i == C::IN_PT - 1) ok = ok && last_live;
+            rin[i] = buf_load(rx, ok ? tb + rl : VCG_OOB);
+        }
+    };
+    auto store_tile = [&](float* buf) {
+#pragma unroll
+        for (int i = 0; i < C::IN_PT; ++i) {
+            const int e = tid + i * 256;
+            if (e < C::IN_ELEMS) buf[e] = rin[i];
+        }
+    };
+    load_tile(n, ty, tx);
+
+    // ---- the weight slab of this block, once per workgroup: row k = (ci, tap) of element tid + 256 i is wave-uniform,
+    // the lane is the output channel.  Rows past KT, channels past cin and columns past cout get VCG_OOB and read 0:
+    // the row's scalar offset is added to the column's with a saturating add, so VCG_OOB stays out of range.  All
+    // loads are issued before the first LDS store; flip and the (tap, ci) decode happen here only
+    {
+        const vcg_rsrc rwt = make_rsrc(p.w, (size_t)C::T * p.cin * p.cout * sizeof(float));
+        const int wvu = __builtin_amdgcn_readfirstlane(wv);
+        const unsigned col = co0 + lane < p.cout ? 4u * (unsigned)(co0 + lane) : VCG_OOB;
+        float rw[C::W_PT];
+#pragma unroll
+        for (int i = 0; i < C::W_PT; ++i) {
+            const int k = wvu + 4 * i;
+            const int ci = k / C::T, tt = k % C::T;
+            const int tap = p.flip ? (C::T - 1 - tt) : tt;
+            const unsigned row = (k < C::KT && ci < p.cin) ? 4u * (unsigned)((tap * p.cin + ci) * p.cout) : VCG_OOB;
+            rw[i] = buf_load(rwt, __builtin_elementwise_add_sat(col, row));
+        }
+        if (tid < 8) s_in[(tid >> 2) * C::IN_BUF + C::IN_ELEMS + (tid & 3)] = 0.f;
+#pragma unroll
+        for (int i = 0; i < C::W_PT; ++i) s_w[tid + i * 256] = rw[i];
     }
-    __syncthreads();
+    store_tile(s_in);
+    lds_barrier();
 
-    f32x16 acc[2][2][1];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][0][r] = 0.f;
-
-    const float* b0p = s_in + (wv * 2 * S) * C::IW + l31 * S;     // lanes 0-31: k even
-    const float* bb1 = b0p + half * 1;                             // lanes 32-63: next tap in the row
-    const float* bb2 = b0p + half * C::D_ROW;                      //              first tap of the next row
-    const float* bb3 = b0p + half * C::D_CH;                       //              first tap of the next channel
     const float* abase = s_w + half * 64 + l31;
+    const float* b0p = s_in + (wv * 2 * S) * C::IW + l31 * S;     // lanes 0-31: k even (buffer 0)
+    int cur = 0;
+    for (;;) {
+        // the next tile's coordinates, and its loads in flight under this tile's MFMAs
+        const bool more = step < tiles - t;
+        const int n0 = n, oy0 = ty * C::ROWS, ox0 = tx * 32;
+        if (more) {
+            t += step;
+            tx += dtx;
+            const int cx = tx >= p.tiles_x ? 1 : 0;
+            tx -= cx ? p.tiles_x : 0;
+            ty += dty + cx;
+            const int cy = ty >= p.tiles_y ? 1 : 0;
+            ty -= cy ? p.tiles_y : 0;
+            n += dn + cy;
+            load_tile(n, ty, tx);
+        }
+
+        f32x16 acc[2][2][1];
 #pragma unroll
-    for (int pr = 0; pr < C::NP; ++pr) {
-        constexpr int dummy = 0; (void)dummy;
-        const int k0 = 2 * pr, k1 = 2 * pr + 1;
-        const int o0 = C::off(k0);
-        const int d = (k1 < C::KT) ? (C::off(k1) - o0) : 1;       // past the end: weights are zero, any valid read
-        const float* bb = (d == 1) ? bb1 : (d == C::D_ROW ? bb2 : bb3);
-        const float a0 = abase[k0 * 64];
-        const float a1 = abase[k0 * 64 + 32];
-        const float v0 = bb[o0];
-        const float v1 = bb[o0 + S * C::IW];
-        acc[0][0][0] = mfma32(a0, v0, acc[0][0][0]);
-        acc[0][1][0] = mfma32(a0, v1, acc[0][1][0]);
-        acc[1][0][0] = mfma32(a1, v0, acc[1][0][0]);
-        acc[1][1][0] = mfma32(a1, v1, acc[1][1][0]);
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][0][r] = 0.f;
+
+        const float* b0 = b0p + cur * C::IN_BUF;
+        const float* bb1 = b0 + half * 1;                              // lanes 32-63: next tap in the row
+        const float* bb2 = b0 + half * C::D_ROW;                       //              first tap of the next row
+        const float* bb3 = b0 + half * C::D_CH;                        //              first tap of the next channel
+        // operands are read one k-pair ahead of the MFMAs that use them, the order pinned as in conv_fwd_kernel: without
+        // it hipcc gathers the reads of a short loop (4x4: 96) in front of it and spills what the tile loop carries
+        auto rd = [&](int pr, float (&f)[4]) {
+            const int k0 = 2 * pr, k1 = 2 * pr + 1;
+            const int o0 = C::off(k0);
+            const int d = (k1 < C::KT) ? (C::off(k1) - o0) : 1;       // past the end: the weight row is zero, the word read a staged value or a zero word
+            const float* bb = (d == 1) ? bb1 : (d == C::D_ROW ? bb2 : bb3);
+            f[0] = abase[k0 * 64];
+            f[1] = abase[k0 * 64 + 32];
+            f[2] = bb[o0];
+            f[3] = bb[o0 + S * C::IW];
+        };
+        float f_[2][4];
+        rd(0, f_[0]);
+#pragma unroll
+        for (int pr = 0; pr < C::NP; ++pr) {
+            const float(&f)[4] = f_[pr & 1];
+            if (pr + 1 < C::NP) rd(pr + 1, f_[(pr & 1) ^ 1]);
+            acc[0][0][0] = mfma32(f[0], f[2], acc[0][0][0]);
+            acc[0][1][0] = mfma32(f[0], f[3], acc[0][1][0]);
+            acc[1][0][0] = mfma32(f[1], f[2], acc[1][0][0]);
+            acc[1][1][0] = mfma32(f[1], f[3], acc[1][1][0]);
+            if (pr + 1 < C::NP) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);   // DS reads of the next pair first
+            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                        // then this pair's MFMAs
+        }
+        // the other buffer was last read one tile ago, in front of the barrier every wave has passed since: one barrier
+        // per tile.  It orders LDS only, so this tile's stores to y stay in flight under the next tile's MFMAs
+        if (more) {
+            store_tile(s_in + (cur ^ 1) * C::IN_BUF);
+            lds_barrier();
+        }
+        conv_epilogue<1>(p, acc, n0, co0, oy0, ox0, wv, lane);
+        if (!more) break;
+        cur ^= 1;
     }
-    conv_epilogue<1>(p, acc, n, co0, oy0, ox0, wv, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -670,6 +762,16 @@ int launch_conv(ConvParams p, hipStream_t st) {
     return launch_with_lds(conv_fwd_kernel<KH, KW, S, CK, XT>, (int)grid, C::LDS_BYTES, p, st);
 }
 
+// compute units of the device, asked once (the devices of one process are alike); 0 if the runtime cannot say
+int device_cu_count() {
+    static const int cus = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+        return v;
+    }();
+    return cus;
+}
+
 template <int KH, int KW, int S>
 int launch_c3(ConvParams p, hipStream_t st) {
     using C = C3Cfg<KH, KW, S>;
@@ -677,8 +779,14 @@ int launch_c3(ConvParams p, hipStream_t st) {
     p.tiles_x = ceil_div(p.ow, 32);
     p.tiles_y = ceil_div(p.oh, C::ROWS);
     p.co_blocks = ceil_div(p.cout, 64);
-    const long grid = (long)p.tiles_x * p.tiles_y * p.co_blocks * p.n;
-    if (grid <= 0 || grid > 0x7fffffffL) return VCG_E_SHAPE;
+    const long tiles = (long)p.tiles_x * p.tiles_y * p.co_blocks * p.n;
+    if (tiles <= 0 || tiles > 0x7fffffffL) return VCG_E_SHAPE;
+    // persistent: two workgroups per CU (the kernel's launch bounds), a whole number of them per channel block
+    const int cus = device_cu_count();
+    if (cus <= 0) return VCG_E_UNSUPPORTED;
+    long grid = tiles < 2L * cus ? tiles : 2L * cus;
+    grid -= grid % p.co_blocks;
+    if (grid < p.co_blocks) grid = p.co_blocks;
     return launch_with_lds(conv_c3_kernel<KH, KW, S>, (int)grid, C::LDS_BYTES, p, st);
 }
 
