@@ -86,6 +86,12 @@ int vcg_conv2d_fwd_stats(const vcg_conv_desc* d, const float* x, const float* w_
 /* dx = dL/dx given dy; `residual` (optional, shape of dx) is added: dx = dgrad + residual */
 int vcg_conv2d_dgrad(const vcg_conv_desc* d, const float* dy, const float* w_hwio, const float* w_hwoi,
                      float* dx, const float* residual, vcg_stream_t stream);
+/* vcg_conv2d_fwd with an inference-mode normalisation between the bias and the activation: y = act(fma(scale[c], conv + bias, shift[c])) +
+ * residual, scale / shift [cout] as vcg_norm_finalize / vcg_norm_finalize_batch write them from the moving statistics (the weights are never
+ * scaled).  The stored values have the bits of vcg_conv2d_fwd (bias only) followed by vcg_norm_act_fwd.  Stride 1, 3x3 or 5x5, more than 3
+ * input channels and more than 32 / kw output channels; VCG_E_UNSUPPORTED otherwise, before anything is launched (run the two calls). */
+int vcg_conv2d_fwd_affine(const vcg_conv_desc* d, const float* x, const float* w_hwio, float* y, const vcg_epilogue* ep, const float* scale,
+                          const float* shift, vcg_stream_t stream);
 size_t vcg_conv2d_wgrad_workspace_bytes(const vcg_conv_desc* d);
 /* dw_hwio (overwritten), dbias (overwritten, may be NULL) */
 int vcg_conv2d_wgrad(const vcg_conv_desc* d, const float* x, const float* dy, float* dw_hwio, float* dbias,
@@ -127,6 +133,10 @@ int vcg_bn_fold(const float* bias, const float* moving_mean, const float* moving
 /* the same for `count` (<= 48) pairs in one launch: HOST arrays of device pointers (bias / gamma / beta entries may be NULL); scale, shift [count][c] */
 int vcg_bn_fold_batch(const float* const* bias, const float* const* moving_mean, const float* const* moving_var, const float* const* gamma,
                       const float* const* beta, int count, int c, float eps, float* scale, float* shift, vcg_stream_t stream);
+/* vcg_norm_finalize's scale / shift (no moving-average update, no bias folded in) for `count` (<= 48) normalisations of c channels in one
+ * launch: HOST arrays of device pointers (gamma / beta entries may be NULL); scale, shift [count][c] */
+int vcg_norm_finalize_batch(const float* const* mean, const float* const* var, const float* const* gamma, const float* const* beta, int count,
+                            int c, float eps, float* scale, float* shift, vcg_stream_t stream);
 /* the same from partial records written by a convolution's epilogue (vcg_epilogue_bf16.stats, vcg_conv2d_nhwc_bf16_fwd_stats):
  * part fp32 [groups][nrec][2][c] = per-record sums and sums of squares over `count` values per group and channel in all; groups = 1
  * (batch statistics; only then are the moving averages updated) or n (instance norm).  Writes mean, scale, shift, invstd [groups*c].

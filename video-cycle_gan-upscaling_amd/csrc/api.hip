@@ -5,7 +5,8 @@
 
 int vcg_internal_conv(const float* x, const float* w, float* y, int n, int cin, int h, int wd, int cout, int oh,
                       int ow, int kh, int kw, int stride, int pad_top, int pad_left, int flip, const vcg_epilogue* ep,
-                      int smallm, int ws_t, int ws_m, int ws_k, hipStream_t st, float* stats = nullptr);
+                      int smallm, int ws_t, int ws_m, int ws_k, hipStream_t st, float* stats = nullptr, const float* scale = nullptr,
+                      const float* shift = nullptr);
 int vcg_internal_convt(const float* x, const float* w, float* y, int n, int cin, int h, int wd, int cout, int oh,
                        int ow, int k, int cby, int cbx, const vcg_epilogue* ep, hipStream_t st);
 size_t vcg_internal_wgrad_ws(int n, int mtot, int ah, int aw, int jctot, int kh, int kw, int S);
@@ -101,6 +102,20 @@ int vcg_conv2d_fwd_stats(const vcg_conv_desc* d, const float* x, const float* w_
     ep.act = VCG_ACT_NONE;
     return vcg_internal_conv(x, w_hwio, y, d->n, d->cin, d->h, d->w, d->cout, d->oh, d->ow, d->kh, d->kw, d->stride, d->pad_top, d->pad_left, 0,
                              &ep, 0, d->cin * d->cout, 1, d->cout, (hipStream_t)stream, stats);
+}
+
+// vcg_conv2d_fwd -> vcg_norm_finalize (inference form) -> vcg_norm_act_fwd as one launch: y = act(fma(scale[c], conv + bias, shift[c])) + residual
+// with the bits of the three-call sequence.  VCG_E_UNSUPPORTED (nothing launched) unless the layer runs in conv_fwd_kernel with the affine
+// epilogue instantiated: stride 1, 3x3 or 5x5, more than 3 input channels, more output channels than the small-M kernel takes.
+int vcg_conv2d_fwd_affine(const vcg_conv_desc* d, const float* x, const float* w_hwio, float* y, const vcg_epilogue* ep, const float* scale,
+                          const float* shift, vcg_stream_t stream) {
+    int rc = check_desc(d);
+    if (rc) return rc;
+    VCG_CHECK_PTR(x); VCG_CHECK_PTR(w_hwio); VCG_CHECK_PTR(y); VCG_CHECK_PTR(scale); VCG_CHECK_PTR(shift);
+    if ((d->oh - 1) * d->stride - d->pad_top >= d->h || (d->ow - 1) * d->stride - d->pad_left >= d->w) return VCG_E_SHAPE;
+    if (use_smallm(d->cout, d->kh, d->kw, d->stride)) return VCG_E_UNSUPPORTED;
+    return vcg_internal_conv(x, w_hwio, y, d->n, d->cin, d->h, d->w, d->cout, d->oh, d->ow, d->kh, d->kw, d->stride, d->pad_top, d->pad_left, 0,
+                             ep, 0, d->cin * d->cout, 1, d->cout, (hipStream_t)stream, nullptr, scale, shift);
 }
 
 int vcg_conv2d_dgrad(const vcg_conv_desc* d, const float* dy, const float* w_hwio, const float* w_hwoi, float* dx,

@@ -35,6 +35,9 @@ struct ConvParams {
     // small-M kernel only: weight element (mch, kc, tap) at w[tap*ws_t + mch*ws_m + kc*ws_k]
     int ws_t, ws_m, ws_k;
     float* stats;          // conv_fwd_kernel<..., STATS>: [n * tiles_y * tiles_x][2][cout] per-tile sums of the accumulators and of their squares
+    // conv_fwd_kernel<..., AFFINE> only: per-channel scale / shift of an inference-mode normalisation between the bias and the activation
+    const float* scale;
+    const float* shift;
 };
 
 template <int KH, int KW, int S, int CK, int XT>
@@ -59,7 +62,11 @@ struct ConvCfg {
 // channels past cout land behind num_records on their own.  The hardware drops what is out of range: one straight-line
 // body, no exec-mask region.  The range check sees the VGPR offset only, which is why nothing sits in soffset.
 // conv_block_fits() (host) keeps 64 planes below 4 GiB.
-template <int XT>
+//
+// AFFINE (an instantiation of its own: the launches without it run the kernels they always ran): v = acc + bias, rounded to fp32 as the stored
+// output of the plain launch is; then v = fma(scale[c], v, shift[c]) and the activation in norm_act_fwd_kernel's form (PReLU as
+// fma(alpha, min(v,0), max(v,0)): apply_act after contraction), so that the result has the bits of vcg_conv2d_fwd -> vcg_norm_act_fwd.
+template <int XT, bool AFFINE = false>
 __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)[2][2][XT], int n, int co0, int oy0, int ox0,
                                               int wv, int lane) {
     const int half = lane >> 5, l31 = lane & 31;
@@ -77,6 +84,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
     const vcg_rsrc rslope = make_rsrc(is_prelu ? p.prelu : nullptr, is_prelu ? (size_t)p.cout * sizeof(float) : 0);
     const float slope_u = (p.act == VCG_ACT_LRELU) ? p.alpha : 1.f;
     const unsigned chan4 = 4u * (unsigned)(co0 + 4 * half);
+    const vcg_rsrc rscale = make_rsrc(AFFINE ? p.scale : nullptr, AFFINE ? (size_t)p.cout * sizeof(float) : 0);
+    const vcg_rsrc rshift = make_rsrc(AFFINE ? p.shift : nullptr, AFFINE ? (size_t)p.cout * sizeof(float) : 0);
 
     const int oy = oy0 + wv * 2, ox = ox0 + l31;
     const unsigned base = (unsigned)(4 * half) * plane4 + (unsigned)oy * ow4 + 4u * (unsigned)ox;
@@ -90,8 +99,9 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
     // 16 elements = RG accumulator rows (channels) make a group; the residual of group g + 1 is requested before group g
     // is stored, so a group never waits for the stores in front of its own loads
     constexpr int RG = 8 / XT, NG = 32 / RG;
-    auto emit = [&](auto res_tag) {
+    auto emit = [&](auto res_tag, auto prelu_tag) {
         constexpr bool RES = decltype(res_tag)::value;
+        constexpr bool PRELU_FMA = decltype(prelu_tag)::value;     // AFFINE with PReLU
         float rs[2][RG][2][XT];
         auto row_of = [](int g, int j) { const int q = g * RG + j, r = q & 15; return (q >> 4) * 32 + (r & 3) + 8 * (r >> 2); };
         auto load_res = [&](int g) {
@@ -107,12 +117,16 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
         if (RES) load_res(0);
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
-            float bv[RG], al[RG];
+            float bv[RG], al[RG], sc[RG], sh[RG];
 #pragma unroll
             for (int j = 0; j < RG; ++j) {
                 bv[j] = buf_load(rbias, chan4 + 4u * (unsigned)row_of(g, j));
                 const float pa = buf_load(rslope, chan4 + 4u * (unsigned)row_of(g, j));
                 al[j] = is_prelu ? pa : slope_u;
+                if (AFFINE) {
+                    sc[j] = buf_load(rscale, chan4 + 4u * (unsigned)row_of(g, j));
+                    sh[j] = buf_load(rshift, chan4 + 4u * (unsigned)row_of(g, j));
+                }
             }
             if (RES && g + 1 < NG) load_res(g + 1);
 #pragma unroll
@@ -124,7 +138,9 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
 #pragma unroll
                     for (int xt = 0; xt < XT; ++xt) {
                         float v = acc[q >> 4][rt][xt][q & 15] + bv[j];
-                        v = v >= 0.f ? v : v * al[j];
+                        if (AFFINE) v = __builtin_fmaf(sc[j], v, sh[j]);
+                        if (PRELU_FMA) v = __builtin_fmaf(al[j], fminf(v, 0.f), fmaxf(v, 0.f));
+                        else v = v >= 0.f ? v : v * al[j];
                         if (RES) v += rs[g & 1][j][rt][xt];
                         buf_store(ry, __builtin_elementwise_add_sat(vo[rt][xt], srow), v);
                     }
@@ -132,7 +148,15 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
             }
         }
     };
-    if (p.residual) emit(std::true_type{}); else emit(std::false_type{});
+    if constexpr (AFFINE) {
+        if (is_prelu) {
+            if (p.residual) emit(std::true_type{}, std::true_type{}); else emit(std::false_type{}, std::true_type{});
+        } else {
+            if (p.residual) emit(std::true_type{}, std::false_type{}); else emit(std::false_type{}, std::false_type{});
+        }
+    } else {
+        if (p.residual) emit(std::true_type{}, std::false_type{}); else emit(std::false_type{}, std::false_type{});
+    }
 }
 
 // STATS epilogue: for the BatchNormalization / instance norm behind the convolution (model.py:19-25, 840) the workgroup also leaves, per output
@@ -176,7 +200,7 @@ __device__ __forceinline__ void conv_stats_epilogue(const ConvParams& p, f32x16 
     }
 }
 
-template <int KH, int KW, int S, int CK, int XT, bool STATS = false>
+template <int KH, int KW, int S, int CK, int XT, bool STATS = false, bool AFFINE = false>
 __global__ __launch_bounds__(256, (KH >= 9 ? 1 : 2)) void conv_fwd_kernel(const ConvParams p) {
     using C = ConvCfg<KH, KW, S, CK, XT>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -322,7 +346,7 @@ __global__ __launch_bounds__(256, (KH >= 9 ? 1 : 2)) void conv_fwd_kernel(const 
         }
     }
 
-    conv_epilogue<XT>(p, acc, n, co0, oy0, ox0, wv, lane);
+    conv_epilogue<XT, AFFINE>(p, acc, n, co0, oy0, ox0, wv, lane);
     if (STATS) conv_stats_epilogue<XT>(p, acc, smem, (n * p.tiles_y + ty) * p.tiles_x + tx, co0, oy0, ox0, wv, lane, tid);
 }
 
@@ -752,10 +776,18 @@ int launch_conv(ConvParams p, hipStream_t st) {
     p.co_blocks = ceil_div(p.cout, 64);
     const long grid = (long)p.tiles_x * p.tiles_y * p.co_blocks * p.n;
     if (grid <= 0 || grid > 0x7fffffffL) return VCG_E_SHAPE;
+    if (p.stats && p.scale) return VCG_E_UNSUPPORTED;
     if (p.stats) {
         // instantiated for the layers a normalisation follows in the fp32 configs: the trunk's 3x3 and the critics' 3x3 / 4x4 stride 1 and 2
         if constexpr ((KH == 3 && KW == 3 && S <= 2) || (KH == 4 && KW == 4 && S <= 2))
             return launch_with_lds(conv_fwd_kernel<KH, KW, S, CK, XT, true>, (int)grid, C::LDS_BYTES, p, st);
+        else
+            return VCG_E_UNSUPPORTED;
+    }
+    // the affine epilogue is instantiated for the stride-1 3x3 / 5x5 layers (the generators' trunks)
+    if (p.scale) {
+        if constexpr (S == 1 && ((KH == 3 && KW == 3) || (KH == 5 && KW == 5)))
+            return launch_with_lds(conv_fwd_kernel<KH, KW, S, CK, XT, false, true>, (int)grid, C::LDS_BYTES, p, st);
         else
             return VCG_E_UNSUPPORTED;
     }
@@ -811,10 +843,14 @@ int vcg_internal_conv9_rowchain(const float* x, const float* w, float* y, int n,
 // contiguous (or addressed by ws_* strides for the small-M kernel).
 int vcg_internal_conv(const float* x, const float* w, float* y, int n, int cin, int h, int wd, int cout,
                       int oh, int ow, int kh, int kw, int stride, int pad_top, int pad_left, int flip,
-                      const vcg_epilogue* ep, int smallm, int ws_t, int ws_m, int ws_k, hipStream_t st, float* stats) {
+                      const vcg_epilogue* ep, int smallm, int ws_t, int ws_m, int ws_k, hipStream_t st, float* stats, const float* scale, const float* shift) {
     ConvParams p{};
     p.x = x; p.w = w; p.y = y; p.stats = stats;
     if (stats && (smallm || cin <= 3)) return VCG_E_UNSUPPORTED;
+    // scale / shift: the affine stage exists in conv_fwd_kernel's epilogue only (conv_c3_kernel<9,9,1> has no register to spare for it)
+    if (scale && (smallm || stats || cin <= 3)) return VCG_E_UNSUPPORTED;
+    if (scale && shift == nullptr) return VCG_E_NULL;
+    p.scale = scale; p.shift = scale ? shift : nullptr;
     p.bias = ep ? ep->bias : nullptr;
     p.prelu = ep ? ep->prelu_alpha : nullptr;
     p.residual = ep ? ep->residual : nullptr;
@@ -854,10 +890,11 @@ int vcg_internal_conv(const float* x, const float* w, float* y, int n, int cin, 
     // MFMA, and 1024 workgroups = 2 full rounds of 2 per CU at the C2 trunk shape instead of 2.67 rounds of 3)
     const bool wide = ow > 32;
     if (kh == 3 && kw == 3 && stride == 1) return wide ? launch_conv<3, 3, 1, 8, 2>(p, st) : launch_conv<3, 3, 1, 8, 1>(p, st);
+    if (kh == 5 && kw == 5 && stride == 1) return launch_conv<5, 5, 1, 8, 1>(p, st);   // XT=2 spills (50 weight prefetch registers)
+    if (scale) return VCG_E_UNSUPPORTED;                     // every other instantiation: see launch_conv
     if (kh == 3 && kw == 3 && stride == 2) return launch_conv<3, 3, 2, 8, 1>(p, st);
     if (kh == 4 && kw == 4 && stride == 1) return launch_conv<4, 4, 1, 8, 1>(p, st);   // XT=2 spills here (measured slower)
     if (kh == 4 && kw == 4 && stride == 2) return launch_conv<4, 4, 2, 4, 1>(p, st);
-    if (kh == 5 && kw == 5 && stride == 1) return launch_conv<5, 5, 1, 8, 1>(p, st);   // XT=2 spills (50 weight prefetch registers)
     if (kh == 5 && kw == 5 && stride == 2) return launch_conv<5, 5, 2, 4, 1>(p, st);
     if (kh == 5 && kw == 5 && stride == 3) return launch_conv<5, 5, 3, 4, 1>(p, st);   // sparse_512 blocks 2-6 (model.py:971-987)
     if (kh == 9 && kw == 9 && stride == 1) return launch_conv<9, 9, 1, 4, 1>(p, st);

@@ -194,6 +194,24 @@ __global__ void bn_fold_batch_kernel(FoldBatch fb, int c, float eps, float* scal
     shift[l * c + i] = ((fb.bias[l] ? fb.bias[l][i] : 0.f) - fb.mmean[l][i]) * sc + (fb.beta[l] ? fb.beta[l][i] : 0.f);
 }
 
+// finalize_kernel's inference form (scale = gamma * rsqrt(moving_var + eps), shift = beta - moving_mean * scale: no bias folded in, the
+// convolution's epilogue applies them behind its own bias) for every normalisation of a learning-phase-0 pass in one launch
+struct FinalizeBatch {
+    const float* mean[FOLD_BATCH_MAX];
+    const float* var[FOLD_BATCH_MAX];
+    const float* gamma[FOLD_BATCH_MAX];
+    const float* beta[FOLD_BATCH_MAX];
+};
+__global__ void finalize_batch_kernel(FinalizeBatch fb, int c, float eps, float* scale, float* shift) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y;
+    if (i >= c) return;
+    const float is = rsqrtf(fb.var[l][i] + eps);
+    const float g = fb.gamma[l] ? fb.gamma[l][i] : 1.f, bt = fb.beta[l] ? fb.beta[l][i] : 0.f;
+    const float sc = g * is;
+    scale[l * c + i] = sc;
+    shift[l * c + i] = bt - fb.mean[l][i] * sc;
+}
+
 // mean / biased variance from the partial records a convolution's epilogue wrote (part[group][nrec][2][c]: sums, sums of squares of the
 // stored values), then what finalize_kernel does -- one launch instead of statistics partial + final + finalize.
 // block = (group, 64 channels) x 16 record lanes; a thread sums its records (eight in flight) in double, the 16 lanes combine in a
@@ -347,8 +365,11 @@ __global__ __launch_bounds__(256) void norm_bwd_partial_kernel(const float* x, c
     }
 }
 
-// combine slices -> sums[G][3]; channel-level dgamma/dbeta/dalpha summed over n for instance mode
-__global__ void norm_bwd_final_kernel(const float* part, int groups, int split, float* sums /* [G][3] */) {
+// combine slices -> sums[G][3]; channel-level dgamma/dbeta/dalpha summed over n for instance mode (norm_bwd_params_kernel).  In batch
+// mode a group IS a channel and its sums are the parameter gradients: PARAMS writes them here, and the launch of their own is gone.
+template <bool PARAMS>
+__global__ void norm_bwd_final_kernel(const float* part, int groups, int split, float* sums /* [G][3] */, float* dgamma, float* dbeta,
+                                      float* dalpha) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= groups) return;
     float a = 0.f, b = 0.f, c = 0.f;
@@ -357,6 +378,11 @@ __global__ void norm_bwd_final_kernel(const float* part, int groups, int split, 
         a += o[0]; b += o[1]; c += o[2];
     }
     sums[g * 3 + 0] = a; sums[g * 3 + 1] = b; sums[g * 3 + 2] = c;
+    if (PARAMS) {
+        if (dbeta) dbeta[g] = a;
+        if (dgamma) dgamma[g] = b;
+        if (dalpha) dalpha[g] = c;
+    }
 }
 
 __global__ void norm_bwd_params_kernel(const float* sums, int n, int c, int mode, float* dgamma, float* dbeta,
@@ -491,6 +517,20 @@ int vcg_bn_fold_batch(const float* const* bias, const float* const* moving_mean,
     return VCG_OK;
 }
 
+int vcg_norm_finalize_batch(const float* const* mean, const float* const* var, const float* const* gamma, const float* const* beta, int count,
+                            int c, float eps, float* scale, float* shift, vcg_stream_t stream) {
+    VCG_CHECK_PTR(mean); VCG_CHECK_PTR(var); VCG_CHECK_PTR(gamma); VCG_CHECK_PTR(beta); VCG_CHECK_PTR(scale); VCG_CHECK_PTR(shift);
+    if (c <= 0 || count <= 0 || count > FOLD_BATCH_MAX) return VCG_E_SHAPE;
+    FinalizeBatch fb;
+    for (int i = 0; i < count; ++i) {
+        VCG_CHECK_PTR(mean[i]); VCG_CHECK_PTR(var[i]);
+        fb.mean[i] = mean[i]; fb.var[i] = var[i]; fb.gamma[i] = gamma[i]; fb.beta[i] = beta[i];
+    }
+    hipLaunchKernelGGL(finalize_batch_kernel, dim3(ceil_div(c, 256), count), dim3(256), 0, (hipStream_t)stream, fb, c, eps, scale, shift);
+    VCG_LAUNCH_CHECK();
+    return VCG_OK;
+}
+
 int vcg_norm_finalize_partials(const float* part, int nrec, int groups, int c, double count, const float* gamma, const float* beta,
                                float eps, float* mean, float* scale, float* shift, float* invstd, float* moving_mean,
                                float* moving_var, float momentum, int unbiased_count, vcg_stream_t stream) {
@@ -573,13 +613,20 @@ int vcg_norm_act_bwd(const float* x, const float* dy, int n, int c, int hw, int 
         hipLaunchKernelGGL(norm_bwd_partial_kernel<false>, dim3(groups * split), dim3(256), 0, st, x, dy, gm, M, split, mean,
                            invstd, gamma, beta, act, act_alpha, prelu_alpha, part);
     VCG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(norm_bwd_final_kernel, dim3(ceil_div(groups, 256)), dim3(256), 0, st, (const float*)part, groups,
-                       split, sums);
-    VCG_LAUNCH_CHECK();
-    if (dgamma || dbeta || dprelu_alpha) {
-        hipLaunchKernelGGL(norm_bwd_params_kernel, dim3(ceil_div(c, 256)), dim3(256), 0, st, (const float*)sums, n, c,
-                           mode, dgamma, dbeta, dprelu_alpha);
+    if (mode != VCG_NORM_INSTANCE) {
+        // batch mode: the combined sums are the parameter gradients, written by the same launch
+        hipLaunchKernelGGL(norm_bwd_final_kernel<true>, dim3(ceil_div(groups, 256)), dim3(256), 0, st, (const float*)part, groups,
+                           split, sums, dgamma, dbeta, dprelu_alpha);
         VCG_LAUNCH_CHECK();
+    } else {
+        hipLaunchKernelGGL(norm_bwd_final_kernel<false>, dim3(ceil_div(groups, 256)), dim3(256), 0, st, (const float*)part, groups,
+                           split, sums, nullptr, nullptr, nullptr);
+        VCG_LAUNCH_CHECK();
+        if (dgamma || dbeta || dprelu_alpha) {
+            hipLaunchKernelGGL(norm_bwd_params_kernel, dim3(ceil_div(c, 256)), dim3(256), 0, st, (const float*)sums, n, c,
+                               mode, dgamma, dbeta, dprelu_alpha);
+            VCG_LAUNCH_CHECK();
+        }
     }
     int gx = ceil_div(hw, vec ? 1024 : 256);
     if (gx > 64) gx = 64;

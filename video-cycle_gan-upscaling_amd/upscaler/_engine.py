@@ -281,6 +281,49 @@ class Conv2D(Layer):
                                           y.data_ptr(), ctypes.byref(ep), rt.stream), "vcg_conv2d_fwd[%s]" % self.name)
         return y, (x, y if self.act != L.ACT_NONE else None, d)
 
+    def forward_prelu(self, x, alpha, training=False, tag=None):
+        """learning phase 0: conv + bias + the PReLU behind the layer (per-channel slopes ``alpha``) in one launch.  The training pass
+        keeps the pre-activation on the tape and runs the two layers."""
+        if training or self.act != L.ACT_NONE:
+            raise NotImplementedError("Conv2D.forward_prelu: the predict pass of a layer without an activation of its own")
+        rt = self.rt
+        n, _, h, w = x.shape
+        d = self.desc(n, h, w)
+        y = rt.empty(n, self.cout, d.oh, d.ow)
+        ep = L.Epilogue(_ptr(self.ps[self.name + "/bias"]), L.ACT_PRELU, 0.0, alpha.data_ptr(), None)
+        with Timed(rt, tag):
+            L.check(rt.lib.vcg_conv2d_fwd(ctypes.byref(d), x.data_ptr(), self.ps[self.name + "/kernel"].data_ptr(),
+                                          y.data_ptr(), ctypes.byref(ep), rt.stream), "vcg_conv2d_fwd[%s]" % self.name)
+        return y
+
+    def forward_folded(self, x, norm, residual=None, folded=None, tag=None):
+        """learning phase 0: conv + BatchNormalization (moving statistics) [+ PReLU / LeakyReLU] [+ Add] in ONE launch: the convolution's
+        epilogue applies the normalisation's per-channel (scale, shift) behind its bias (vcg_conv2d_fwd_affine; the weights are not
+        scaled, and the result has the bits of the separate launches).  norm: the NormAct behind this convolution (batch norm).
+        folded: its (scale, shift) already derived (finalize_batch).  Where the layer's kernel has no such epilogue the convolution and
+        vcg_norm_act_fwd run one after the other."""
+        rt, ps = self.rt, self.ps
+        if self.act != L.ACT_NONE or norm.norm != "batch":
+            raise NotImplementedError("Conv2D.forward_folded: a convolution without activation in front of a BatchNormalization")
+        n, _, h, w = x.shape
+        d = self.desc(n, h, w)
+        if folded is not None:
+            scale, shift = folded
+        else:
+            scale, shift = finalize_batch(rt, [norm])[id(norm)]
+        y = rt.empty(n, self.cout, d.oh, d.ow)
+        ep = L.Epilogue(_ptr(ps[self.name + "/bias"]), norm.act, float(norm.alpha), norm._alpha_ptr(), _ptr(residual))
+        with Timed(rt, tag):
+            rc = rt.lib.vcg_conv2d_fwd_affine(ctypes.byref(d), x.data_ptr(), ps[self.name + "/kernel"].data_ptr(), y.data_ptr(), ctypes.byref(ep),
+                                              scale.data_ptr(), shift.data_ptr(), rt.stream)
+        if rc != L.E_UNSUPPORTED:
+            L.check(rc, "vcg_conv2d_fwd_affine[%s]" % self.name)
+            return y
+        z, _ = self.forward(x, tag=tag)
+        L.check(rt.lib.vcg_norm_act_fwd(z.data_ptr(), n, self.cout, d.oh * d.ow, scale.data_ptr(), shift.data_ptr(), 0, norm.act, float(norm.alpha),
+                                        norm._alpha_ptr(), _ptr(residual), y.data_ptr(), rt.stream), "vcg_norm_act_fwd[%s]" % norm.name)
+        return y
+
     def forward_stats(self, x, instance, tag=None):
         """forward (bias, no activation) whose epilogue leaves the statistics of the normalisation behind the layer: returns
         (y, ctx, (records, records per group, shift)) for NormAct.forward(stats=...), or stats None where the layer's kernel has no
@@ -444,6 +487,26 @@ class ConvTDilated(ConvT2D):
             L.check(rt.lib.vcg_channel_sum(dy.data_ptr(), d.n, self.cout, d.h * d.w, self.ps.grad(self.name + "/bias", which).data_ptr(), ws, wsn,
                                            rt.stream), "vcg_channel_sum[%s]" % self.name)
         return None
+
+
+def finalize_batch(rt, norms):
+    """{id(norm): (scale, shift)} of the fp32 batch-norm NormActs of a learning-phase-0 pass from their moving statistics: one
+    vcg_norm_finalize_batch launch per 48 layers of equal width (what NormAct.forward(training=False) derives per layer)"""
+    out = {}
+    by_c = {}
+    for nm in norms:
+        by_c.setdefault(nm.c, []).append(nm)
+    for c, group in by_c.items():
+        for at in range(0, len(group), 48):
+            part = group[at:at + 48]
+            n = len(part)
+            buf = rt.empty(2, n, c)
+            col = lambda key: (ctypes.c_void_p * n)(*[nm.ps[nm.name + key].data_ptr() for nm in part])
+            L.check(rt.lib.vcg_norm_finalize_batch(col("/moving_mean"), col("/moving_variance"), col("/gamma"), col("/beta"), n, c, BN_EPS,
+                                                   buf[0].data_ptr(), buf[1].data_ptr(), rt.stream), "vcg_norm_finalize_batch")
+            for i, nm in enumerate(part):
+                out[id(nm)] = (buf[0, i], buf[1, i])
+    return out
 
 
 class NormAct(Layer):

@@ -51,6 +51,8 @@ SIGNATURES = {
     "vcg_error_string": (c_char_p, [c_int]),
     "vcg_conv2d_fwd": (c_int, [_D, _P, _P, _P, _E, _P]),
     "vcg_conv2d_dgrad": (c_int, [_D, _P, _P, _P, _P, _P, _P]),
+    "vcg_conv2d_fwd_affine": (c_int, [_D, _P, _P, _P, _E, _P, _P, _P]),
+    "vcg_norm_finalize_batch": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, _P, _P, _P]),
     "vcg_conv2d_wgrad_workspace_bytes": (c_size_t, [_D]),
     "vcg_conv2d_wgrad": (c_int, [_D, _P, _P, _P, _P, _P, c_size_t, _P]),
     "vcg_conv_transpose2d_fwd": (c_int, [_D, _P, _P, _P, _E, _P]),

@@ -463,8 +463,11 @@ class UpscalerOrig(Model):
         if self.init_bf16:
             h, c = self.c_init.forward_prelu(x, self.ps[self.a_init.prelu_name + "/alpha"], training); tape.extend((c, None))
         else:
-            h, c = self.c_init.forward(x); tape.append(c)
-            h, c = self.a_init.forward(h, training); tape.append(c)
+            if training or self.trunk_dtype == "bf16":
+                h, c = self.c_init.forward(x); tape.append(c)
+                h, c = self.a_init.forward(h, training); tape.append(c)
+            else:                                   # fp32 predict: the PReLU in the convolution's epilogue, nothing kept for a backward
+                h = self.c_init.forward_prelu(x, self.ps[self.a_init.prelu_name + "/alpha"]); tape.extend((None, None))
             if self.trunk_dtype == "bf16":          # the trunk (2*res+1 convolutions, norms, adds) on bf16 NHWC; fp32 outside
                 h = E.to_bf16_nhwc(self.rt, h)
         skip = h
@@ -473,6 +476,12 @@ class UpscalerOrig(Model):
         if bf and not training and self.n_pre.norm == "batch" and len(self.blocks) * 2 + 1 <= 48:
             # every folded BatchNormalization of the pass in one launch
             folds = E.fold_batch(self.rt, [p for b in self.blocks for p in ((b[0], b[1]), (b[2], b[3]))] + [(self.c_pre, self.n_pre)])
+        fold32 = not bf and not training and self.n_pre.norm == "batch"
+        if fold32:
+            # fp32: the moving statistics' (scale, shift) of every BatchNormalization of the pass in one launch, applied by the
+            # convolutions' epilogues behind their bias
+            f32 = E.finalize_batch(self.rt, [nm for b in self.blocks for nm in (b[1], b[3])] + [self.n_pre])
+            folds = {id(cv): f32[id(nm)] for cv, nm in [p for b in self.blocks for p in ((b[0], b[1]), (b[2], b[3]))] + [(self.c_pre, self.n_pre)]}
 
         def conv_norm(cv, nm, h, residual=None):
             """conv -> norm[-> act][+ residual]; on the bf16 trunk the convolution's epilogue hands the norm its statistics, and in
@@ -480,6 +489,9 @@ class UpscalerOrig(Model):
             if bf and not training and nm.norm == "batch":
                 tape.extend((None, None))
                 return cv.forward_folded(h, nm, residual=residual, tag="trunk_conv", folded=folds.get(id(cv)))
+            if fold32:
+                tape.extend((None, None))
+                return cv.forward_folded(h, nm, residual=residual, folded=folds.get(id(cv)), tag="trunk_conv")
             if nm.needs_stats(training):          # (both dtypes: the convolution's epilogue hands the norm its statistics)
                 h, a, st = cv.forward_stats(h, nm.norm == "instance", tag="trunk_conv"); tape.append(a)
                 h, a = nm.forward(h, training, residual=residual, stats=st); tape.append(a)
