@@ -417,6 +417,16 @@ size_t vcg_conv_in_gate_bf16_wfrag_bytes(int32_t cin, int32_t kh, int32_t kw, in
 int vcg_pack_conv_in_gate_bf16(const void* w_hwio, int32_t cin, int32_t kh, int32_t kw, int32_t cout, void* out, hipStream_t stream);
 int vcg_conv_in_gate_bf16_fwd(const vcg_conv_desc* d, const void* u, const void* wfrag, const void* bias, const void* m, void* y,
                               hipStream_t stream);
+/* The backward of that gate in a residual_block_attention (what Keras derives from upscaling/upscaler/model.py:33-36), one launch:
+ * s = sigmoid(conv_k(u) + bias) is recomputed from the frames -- in training the attention tensor does not reach HBM either --,
+ *   dm = bf16(dy * s + dres)          the gradient at m; dres (bf16 NHWC, may be NULL) is a gradient that joins there (the block's Add):
+ *                                     the sum is formed in fp32 and rounded once, the rule of vcg_conv2d_nhwc_bf16_dgrad_add; with
+ *                                     dres NULL dm has the bits of a dres of zeros
+ *   da = bf16(dy * m * s * (1 - s))   the gradient in front of the gate convolution's bias: the dz vcg_conv3ch_bf16_wgrad reads
+ * u, wfrag, bias, m as in the forward; dy, dres, dm, da: bf16 NHWC [n][h][w][64].  cin 3, k x k = 3x3 or 5x5, stride 1, pads k/2, cout 64;
+ * anything else, and dm == dres, dm == m or dm == da, returns VCG_E_UNSUPPORTED before any launch.  No workspace, no scratch memory. */
+int vcg_conv_in_gate_bf16_bwd(const vcg_conv_desc* d, const void* u, const void* wfrag, const void* bias, const void* m, const void* dy,
+                              const void* dres, void* dm, void* da, hipStream_t stream);
 
 /* to_add_input of upsampling_block_attention (upscaling/upscaler/model.py:94-97), in place on the bf16 NHWC output y [n][s h][s w][cout] of the
  * stage's LeakyReLU:  y = bf16(y + bias[c] + Conv2DTranspose(cout, s+1, strides s, 'same')(atanh(0.99999 x))[c]), x the fp32 NCHW frames
@@ -434,7 +444,8 @@ int vcg_conv3ch_bf16_dgrad(const vcg_conv_desc* d, const void* dz, const float* 
 /* weight (+ bias) gradient of a layer that reads the 3-channel frames -- initial/conv (9x9, upscaling/upscaler/model.py:275), the critics'
  * first layers (3x3 'same', model.py:839, 904; the PatchGAN's 4x4 stride 2) -- from the fp32 NCHW frames x [n][3][h][w] and the bf16 NHWC gradient
  * dz [n][oh][ow][cout] in front of the layer's activation: both as bf16 MFMA operands (the roundings the forward kernel multiplies), fp32
- * accumulation, dw in Keras' (kh,kw,3,cout) layout, dbias [cout] or NULL; deterministic.  cout % 64 == 0, even width; VCG_E_UNSUPPORTED
+ * accumulation, dw in Keras' (kh,kw,3,cout) layout, dbias [cout] or NULL; deterministic.  Also the 5x5 and 3x3 gates of
+ * residual_block_attention (model.py:33) from vcg_conv_in_gate_bf16_bwd's da.  cout % 64 == 0, even width; VCG_E_UNSUPPORTED
  * otherwise (run vcg_conv2d_wgrad on an fp32 copy of dz).  Replaces the gradient of model.py:275 / :839 that Keras derives. */
 size_t vcg_conv3ch_bf16_wgrad_workspace_bytes(const vcg_conv_desc* d);
 int vcg_conv3ch_bf16_wgrad(const vcg_conv_desc* d, const float* x, const void* dz, float* dw_hwio, float* dbias, void* ws, size_t ws_bytes,

@@ -693,13 +693,20 @@ struct I9Params {
     const float* x;          // fp32 NCHW [n][3][h][w]
     const uint4* w;          // packed fragments (vcg_pack_first9x9_bf16)
     const float* bias;       // [cout] or null
-    const float* alpha;      // PReLU slopes [cout] or null (none)
+    union {
+        const float* alpha;  // PReLU slopes [cout] or null (none)
+        const __bf16* dy;    // GATE_BWD: the gradient at the gate's output, bf16 NHWC [n][h][w][cout]
+    };
     __bf16* y;               // bf16 NHWC [n][h][w][cout]
-    __bf16* z;               // optional bf16 NHWC [n][h][w][cout]: the value in front of the PReLU (its backward needs the sign and, for the slope gradient, the value)
+    __bf16* z;               // optional bf16 NHWC [n][h][w][cout]: the value in front of the PReLU (its backward needs the sign and, for the slope gradient, the value);
+                             // GATE_BWD: da, the gradient in front of the gate convolution's bias (y is dm)
     const __bf16* mask;      // optional bf16 NHWC [n][h][w][cout]: y *= (mask > 0 ? 1 : mask_slope)  (data gradient in front of a LeakyReLU);
                              // GATE instantiations: the gated tensor m, y = sigmoid(conv + bias) * m
     float mask_slope;
-    float* chsum;            // optional [workgroups per channel block * 6][cout]: per-wave sums of the stored output per channel (a bias gradient)
+    union {
+        float* chsum;        // optional [workgroups per channel block * 6][cout]: per-wave sums of the stored output per channel (a bias gradient)
+        const __bf16* dres;  // GATE_BWD: optional bf16 NHWC gradient joining at m, added to dm in fp32 before the one rounding
+    };
     int n, h, w_, cout, tiles_x, tiles_y, total;        // cout = 64 * nblk; workgroup b serves channel block b % nblk; h, w_: INPUT size
     int oh, ow, pad_top, pad_left;                      // output size and the 'before' pads (9x9 'same': h, w_, 4, 4)
     float slope;                                        // without alpha: LeakyReLU slope (1 = no activation)
@@ -716,10 +723,26 @@ VCG_STAMP_SUMS(i9, 512 * 8 * 6);
 // gives rcp(inf) = 0, exp -> 0 gives 1.
 __device__ __forceinline__ float fast_sigmoid(float x) { return __frcp_rn(1.f + __expf(-x)); }
 
+// the same sigmoid (bit for bit) and its slope s (1 - s) = e / (1 + e)^2 with e = exp(-x), formed from e and not as s * (1 - s): at large x the
+// fp32 rounding of s next to 1 leaves 1 - s few significant bits (3e-8 absolute of 6e-6 at x = 12 is 2^-8 relative, a whole bf16 rounding).
+// e * s * s is good to a few fp32 ulp for every x; the clamp keeps e = inf (x < -88, s = 0) from making inf * 0.
+__device__ __forceinline__ float fast_sigmoid_slope(float x, float& s) {
+    const float e = __expf(-x);
+    s = __frcp_rn(1.f + e);
+    return fminf(e, 0x1p+60f) * s * s;
+}
+
+// the epilogue forms of conv_c3to64_bf16_kernel
+constexpr int GATE_NONE = 0;     // bias + PReLU / LeakyReLU [* mask]
+constexpr int GATE_FWD = 1;      // y = bf16(sigmoid(conv + bias) * m)
+constexpr int GATE_BWD = 2;      // s = sigmoid(conv + bias) recomputed;  dm = bf16(dy * s + dres),  da = bf16(dy * m * s * (1 - s))
+
 // GATE (input-driven attention gates of make_upscaler_attention, model.py:33-36, 86-90): the epilogue is y = bf16(sigmoid(conv + bias) * m)
 // with m (p.mask) a bf16 NHWC tensor of the output's shape, requested under the MFMA loop like the LeakyReLU mask; the attention tensor
-// itself never leaves the registers.
-template <int KH, int NG, int S, int NSRC = 1, bool GATE = false>
+// itself never leaves the registers.  GATE_BWD is that gate's backward in the same launch shape: the MFMA loop recomputes the pre-activation
+// from the frames, dy and the joining gradient dres are requested next to m, and the epilogue writes dm (p.y) and da (p.z) -- in training
+// the attention tensor does not reach HBM either.
+template <int KH, int NG, int S, int NSRC = 1, int GATE = GATE_NONE>
 __global__ __launch_bounds__(NT, 1) void conv_c3to64_bf16_kernel(I9Params p) {
     using C = I3Cfg<KH, NG, S, NSRC>;
     constexpr int I_HC = C::HC, I_ROWB = C::ROWB, I_XB = C::XB, I_XB1 = C::XB1, I_WB = C::WB, I_NPIX = C::NPIX, I_NPRE = C::NPRE, NK = C::NK;
@@ -740,7 +763,8 @@ __global__ __launch_bounds__(NT, 1) void conv_c3to64_bf16_kernel(I9Params p) {
     for (int c = tid; c < I_WB / 16; c += NT) ((uint4*)wl)[c] = p.w[(long)cb * (I_WB / 16) + c];
     if (tid < 64) {
         prm[tid] = p.bias ? p.bias[cb * 64 + tid] : 0.f;
-        prm[64 + tid] = p.alpha ? p.alpha[cb * 64 + tid] : p.slope;
+        if constexpr (GATE == GATE_BWD) prm[64 + tid] = 1.f;      // (the alpha slot holds dy)
+        else prm[64 + tid] = p.alpha ? p.alpha[cb * 64 + tid] : p.slope;
     }
     const long plane = (long)p.h * p.w_;
 
@@ -826,7 +850,8 @@ __global__ __launch_bounds__(NT, 1) void conv_c3to64_bf16_kernel(I9Params p) {
         // under the MFMA loop.  (Loaded where it was used, each of the eight 16-byte loads waited out an HBM round trip: 6.6k of a tile's
         // 21k cycles, profiles/r03_i9_stamps.txt.)
         bf16x8 mk[2][2][2];
-        if (GATE || p.mask) {
+        bf16x8 gd[2][2][2], gr[2][2][2];                       // GATE_BWD: dy and dres of the same pixels
+        if (GATE != GATE_NONE || p.mask) {
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -836,6 +861,13 @@ __global__ __launch_bounds__(NT, 1) void conv_c3to64_bf16_kernel(I9Params p) {
                         const int gy = gy0 + pt;
                         const long o = ((long)(img * p.oh + min(gy, p.oh - 1)) * p.ow + min(gx, p.ow - 1)) * p.cout + cb * 64 + mt * 32 + 16 * q + 8 * hh;
                         mk[mt][q][pt] = *(const bf16x8*)(p.mask + o);
+                        if constexpr (GATE == GATE_BWD) {
+                            gd[mt][q][pt] = *(const bf16x8*)(p.dy + o);
+                            // without a joining gradient the sum below still adds a zero: the same bits as a dres of zeros
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) gr[mt][q][pt][j] = (__bf16)0.f;
+                            if (p.dres) gr[mt][q][pt] = *(const bf16x8*)(p.dres + o);
+                        }
                     }
         }
 
@@ -904,7 +936,12 @@ __global__ __launch_bounds__(NT, 1) void conv_c3to64_bf16_kernel(I9Params p) {
                     for (int j = 0; j < 8; ++j) {
                         float u = v[j] + sh[j];
                         zv[j] = (__bf16)u;
-                        if constexpr (GATE) {
+                        if constexpr (GATE == GATE_BWD) {
+                            float s;
+                            const float slope = fast_sigmoid_slope(u, s), g = (float)gd[mt][q][pt][j];
+                            zv[j] = (__bf16)(g * (float)mk[mt][q][pt][j] * slope);                   // da
+                            u = g * s + (float)gr[mt][q][pt][j];                                     // dm: fp32 sum, rounded once
+                        } else if constexpr (GATE == GATE_FWD) {
                             u = fast_sigmoid(u) * (float)mk[mt][q][pt][j];           // fp32 product, rounded once
                         } else {
                             u = u >= 0.f ? u : u * al[j];
@@ -913,8 +950,9 @@ __global__ __launch_bounds__(NT, 1) void conv_c3to64_bf16_kernel(I9Params p) {
                         ov[j] = (__bf16)u;
                     }
                     if (ok) *(bf16x8*)(p.y + o) = ov;
-                    if (!GATE && p.z && ok) *(bf16x8*)(p.z + o) = zv;
-                    if (!GATE && p.chsum && ok) {                             // the values as stored
+                    if (GATE == GATE_BWD && ok) *(bf16x8*)(p.z + o) = zv;
+                    if (GATE == GATE_NONE && p.z && ok) *(bf16x8*)(p.z + o) = zv;
+                    if (GATE == GATE_NONE && p.chsum && ok) {                             // the values as stored
 #pragma unroll
                         for (int j = 0; j < 8; ++j) csum[mt * 16 + q * 8 + j] += (float)ov[j];
                     }
@@ -934,7 +972,7 @@ __global__ __launch_bounds__(NT, 1) void conv_c3to64_bf16_kernel(I9Params p) {
         o[0] = s0, o[1] = s1, o[2] = s2, o[3] = s3, o[4] = ntl, o[5] = __builtin_amdgcn_s_memtime() - k_c0;
     }
 #endif
-    if (!GATE && p.chsum) {
+    if (GATE == GATE_NONE && p.chsum) {
         // lane (r, hh) ends up with the sum of value r = [mt][q][j] over the wave's 32 pixel lanes: channel mt*32 + 16q + 8hh + j
         const float t = half_wave_reduce_scatter32(csum, r);
         p.chsum[(long)(wg0 * NCW + wv) * p.cout + cb * 64 + (r >> 4) * 32 + ((r >> 3) & 1) * 16 + 8 * hh + (r & 7)] = t;
@@ -984,7 +1022,7 @@ __global__ void pack_in_gate_kernel(const float* __restrict__ w, uint4* __restri
 
 }  // namespace
 
-template <int KH, int NG, int S, int NSRC = 1, bool GATE = false>
+template <int KH, int NG, int S, int NSRC = 1, int GATE = GATE_NONE>
 static int launch_conv3ch(I9Params p, hipStream_t stream) {
     using C = I3Cfg<KH, NG, S, NSRC>;
     if (int e = vcg_allow_dyn_lds((const void*)conv_c3to64_bf16_kernel<KH, NG, S, NSRC, GATE>, C::LDS)) return e;
@@ -1149,8 +1187,48 @@ int vcg_conv_in_gate_bf16_fwd(const vcg_conv_desc* d, const void* u, const void*
     p.tiles_x = ceil_div(d->ow, TC);
     p.tiles_y = ceil_div(d->oh, TR);
     p.total = p.n * p.tiles_x * p.tiles_y;
-    if (d->kh == 3) return d->cin == 3 ? launch_conv3ch<3, 1, 1, 1, true>(p, stream) : launch_conv3ch<3, 1, 1, 2, true>(p, stream);
-    return d->cin == 3 ? launch_conv3ch<5, 2, 1, 1, true>(p, stream) : launch_conv3ch<5, 2, 1, 2, true>(p, stream);
+    if (d->kh == 3) return d->cin == 3 ? launch_conv3ch<3, 1, 1, 1, GATE_FWD>(p, stream) : launch_conv3ch<3, 1, 1, 2, GATE_FWD>(p, stream);
+    return d->cin == 3 ? launch_conv3ch<5, 2, 1, 1, GATE_FWD>(p, stream) : launch_conv3ch<5, 2, 1, 2, GATE_FWD>(p, stream);
+}
+
+// The gate's backward (model.py:33-36 differentiated): s = sigmoid(conv_kxk(u) + bias) is recomputed from the frames,
+//   dm = bf16(dy * s + dres)        (dres: a gradient joining at m, or NULL; fp32 sum, one rounding -- vcg_conv2d_nhwc_bf16_dgrad_add's rule)
+//   da = bf16(dy * m * s * (1 - s)) (the gradient in front of the gate convolution's bias: vcg_conv3ch_bf16_wgrad's dz)
+// in one launch, no workspace.  Served: cin 3, 3x3 / 5x5, stride 1, cout 64 (the residual blocks' gates).
+int vcg_conv_in_gate_bf16_bwd(const vcg_conv_desc* d, const void* u, const void* wfrag, const void* bias, const void* m, const void* dy,
+                              const void* dres, void* dm, void* da, hipStream_t stream) {
+    VCG_CHECK_PTR(d);
+    VCG_CHECK_PTR(u);
+    VCG_CHECK_PTR(wfrag);
+    VCG_CHECK_PTR(m);
+    VCG_CHECK_PTR(dy);
+    VCG_CHECK_PTR(dm);
+    VCG_CHECK_PTR(da);
+    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->oh != d->h || d->ow != d->w) return VCG_E_SHAPE;
+    if (d->cin != 3 || d->cout != 64 || d->kh != d->kw || (d->kh != 3 && d->kh != 5) || d->stride != 1 || d->pad_top != d->kh / 2 ||
+        d->pad_left != d->kw / 2)
+        return VCG_E_UNSUPPORTED;
+    if (dm == dres || dm == m || dm == da) return VCG_E_UNSUPPORTED;          // m still feeds the block's Add; dres may be another branch's gradient
+    if ((long)d->n * ceil_div(d->w, TC) * ceil_div(d->h, TR) > 0x7FFFFFFFl) return VCG_E_UNSUPPORTED;
+    I9Params p;
+    p.dres = (const __bf16*)dres;
+    p.x = (const float*)u;
+    p.w = (const uint4*)wfrag;
+    p.bias = (const float*)bias;
+    p.dy = (const __bf16*)dy;
+    p.xcd_group = 0;
+    p.slope = 1.f;
+    p.y = (__bf16*)dm;
+    p.z = (__bf16*)da;
+    p.mask = (const __bf16*)m;
+    p.mask_slope = 0.f;
+    p.n = d->n; p.h = d->h; p.w_ = d->w; p.cout = d->cout;
+    p.oh = d->oh; p.ow = d->ow; p.pad_top = d->pad_top; p.pad_left = d->pad_left;
+    p.tiles_x = ceil_div(d->ow, TC);
+    p.tiles_y = ceil_div(d->oh, TR);
+    p.total = p.n * p.tiles_x * p.tiles_y;
+    if (d->kh == 3) return launch_conv3ch<3, 1, 1, 1, GATE_BWD>(p, stream);
+    return launch_conv3ch<5, 2, 1, 1, GATE_BWD>(p, stream);
 }
 
 int vcg_conv9x9_from3_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* wfrag, const void* bias, const void* prelu_alpha,

@@ -132,11 +132,15 @@ __global__ __launch_bounds__(256, 2) void wgrad3_bf16_kernel(W3Params p) {
         for (int t = 0; t < 2; ++t) fb[set][j][t] = tr_read(lb + bbase[j] + (unsigned)((S * i * C::HCA + S * (cb * 16 + 4 * t)) * 8));
     };
     // s_waitcnt lgkmcnt(0) that also ties the fragment registers of a set to itself (nothing may use them before it)
-    static_assert(C::NTW == 1 || C::NTW == 6, "wgrad3: the fragment sets are tied to the wait by name");
+    static_assert(C::NTW == 1 || C::NTW == 2 || C::NTW == 6, "wgrad3: the fragment sets are tied to the wait by name");
 #define W3_WAIT_SET(S_)                                                                                                                       \
     do {                                                                                                                                      \
         if constexpr (C::NTW == 1) {                                                                                                          \
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[S_][0]), "+v"(fa[S_][1]), "+v"(fb[S_][0][0]), "+v"(fb[S_][0][1]));                 \
+        } else if constexpr (C::NTW == 2) {                                                                                                   \
+            asm volatile("s_waitcnt lgkmcnt(0)"                                                                                               \
+                         : "+v"(fa[S_][0]), "+v"(fa[S_][1]), "+v"(fb[S_][0][0]), "+v"(fb[S_][0][1]), "+v"(fb[S_][C::NTW - 1][0]),            \
+                           "+v"(fb[S_][C::NTW - 1][1]));                                                                                      \
         } else {                                                                                                                              \
             asm volatile("s_waitcnt lgkmcnt(0)"                                                                                               \
                          : "+v"(fa[S_][0]), "+v"(fa[S_][1]), "+v"(fb[S_][0][0]), "+v"(fb[S_][0][1]), "+v"(fb[S_][1][0]), "+v"(fb[S_][1][1]), \
@@ -300,7 +304,7 @@ bool w3_supported(const vcg_conv_desc* d) {
     if (d->cin != 3 || d->cout % 64 || d->kh != d->kw || d->w % 2) return false;
     if ((long)d->h * d->w * 8 > 0xFFFFFFE0l || (long)d->oh * d->ow * d->cout * 2 > 0xFFFFFFE0l) return false;
     if (d->pad_top < 0 || d->pad_left < 0 || d->pad_top >= d->kh || d->pad_left >= d->kw) return false;
-    return (d->kh == 9 && d->stride == 1) || (d->kh == 3 && d->stride == 1) || (d->kh == 4 && d->stride == 2);
+    return (d->kh == 9 && d->stride == 1) || (d->kh == 5 && d->stride == 1) || (d->kh == 3 && d->stride == 1) || (d->kh == 4 && d->stride == 2);
 }
 
 size_t w3_wave_floats(int k) {
@@ -344,6 +348,7 @@ int vcg_conv3ch_bf16_wgrad(const vcg_conv_desc* d, const float* x, const void* d
     pack_frames3_bf16_kernel<<<(unsigned)((px + 255) / 256), 256, 0, stream>>>(x, (__bf16*)xq, d->n, (long)d->h * d->w);
     VCG_LAUNCH_CHECK();
     if (d->kh == 9) return launch_w3<9, 1>(p, dw_hwio, dbias, stream);
+    if (d->kh == 5) return launch_w3<5, 1>(p, dw_hwio, dbias, stream);
     if (d->kh == 3) return launch_w3<3, 1>(p, dw_hwio, dbias, stream);
     return launch_w3<4, 2>(p, dw_hwio, dbias, stream);
 }

@@ -769,12 +769,12 @@ def pack_conv3ch_bf16(rt, w, kh, kw, cout, out=None):
     return out
 
 
-def pack_conv_in_gate_bf16(rt, w, cin, kh, kw, cout):
-    """Conv2D (kh,kw,cin,cout) for vcg_conv_in_gate_bf16_fwd; None where that kernel does not serve the shape"""
+def pack_conv_in_gate_bf16(rt, w, cin, kh, kw, cout, out=None):
+    """Conv2D (kh,kw,cin,cout) for vcg_conv_in_gate_bf16_fwd / _bwd; None where that kernel does not serve the shape"""
     nbytes = rt.lib.vcg_conv_in_gate_bf16_wfrag_bytes(cin, kh, kw, cout)
     if nbytes == 0:
         return None
-    out = _bytes(rt, nbytes)
+    out = _bytes(rt, nbytes) if out is None else out
     L.check(rt.lib.vcg_pack_conv_in_gate_bf16(w.data_ptr(), cin, kh, kw, cout, out.data_ptr(), rt.stream), "vcg_pack_conv_in_gate_bf16")
     return out
 
@@ -1446,6 +1446,52 @@ class StemConv9x9Bf16(InitialConv9x9Bf16):
         if param_grads:
             conv3ch_bf16_wgrad(self, d, x, dz, which, tag)
         return None
+
+
+class GateConvBf16(Conv2D):
+    """The input-driven gate of residual_block_attention (model.py:33-36) as one layer on bf16 NHWC: Conv2D(64, k, 'same') of the fp32 NCHW
+    frames u + sigmoid + Multiply with the block input m.  forward: y = bf16(sigmoid(conv(u) + bias) * m) on vcg_conv_in_gate_bf16_fwd;
+    backward: vcg_conv_in_gate_bf16_bwd recomputes the sigmoid from the frames and writes dm (with the gradient joining at m added before
+    the one rounding) and da, from which vcg_conv3ch_bf16_wgrad takes the gate's weight / bias gradient (odd widths: the fp32 kernel on an
+    fp32 NCHW copy of da).  The attention tensor is never stored; the context is (u, m).  Declares the Conv2D's parameters under the
+    fp32 model's names (res_block/i/attention/kernel, /bias).  The frames are the network input: no gradient goes to u."""
+
+    def __init__(self, name, cin=3, cout=64, k=3):
+        if cin != 3 or cout != 64 or k not in (3, 5):
+            raise NotImplementedError("the bf16 gate is instantiated for 3x3 / 5x5, 3 -> 64 channels")
+        super().__init__(name, cin, cout, k)
+        self._pk = PackedOperand(lambda out: pack_conv_in_gate_bf16(self.rt, self.ps[self.name + "/kernel"], 3, k, k, 64, out), self)
+
+    def _check(self, u, m):
+        n, c, h, w = u.shape
+        if c != 3 or m.dtype != torch.bfloat16 or tuple(m.shape) != (n, h, w, self.cout):
+            raise TypeError("GateConvBf16[%s]: u fp32 NCHW frames [n,3,h,w], m bf16 NHWC [n,h,w,%d]" % (self.name, self.cout))
+        return self.desc(n, h, w)
+
+    def forward(self, u, m, tag=None):
+        rt = self.rt
+        d = self._check(u, m)
+        y = torch.empty_like(m)
+        with Timed(rt, tag):
+            L.check(rt.lib.vcg_conv_in_gate_bf16_fwd(ctypes.byref(d), u.data_ptr(), self._pk.get().data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
+                                                     m.data_ptr(), y.data_ptr(), rt.stream), "vcg_conv_in_gate_bf16_fwd[%s]" % self.name)
+        return y, (u, m)
+
+    def backward(self, ctx, dy, which=0, dx_residual=None, tag=None):
+        """dy: bf16 NHWC gradient at the gate's output; dx_residual: a bf16 NHWC gradient that joins at m (the block's Add) -> dm"""
+        rt = self.rt
+        u, m = ctx
+        d = self._check(u, m)
+        for t in (dy, dx_residual):
+            if t is not None and (t.dtype != torch.bfloat16 or tuple(t.shape) != tuple(m.shape)):
+                raise TypeError("GateConvBf16[%s]: gradients are bf16 NHWC tensors of m's shape" % self.name)
+        dm, da = torch.empty_like(m), torch.empty_like(m)
+        with Timed(rt, tag and tag + "_bwd"):
+            L.check(rt.lib.vcg_conv_in_gate_bf16_bwd(ctypes.byref(d), u.data_ptr(), self._pk.get().data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
+                                                     m.data_ptr(), dy.data_ptr(), _ptr(dx_residual), dm.data_ptr(), da.data_ptr(), rt.stream),
+                    "vcg_conv_in_gate_bf16_bwd[%s]" % self.name)
+        conv3ch_bf16_wgrad(self, d, u, da, which, tag)
+        return dm
 
 
 class NormActBf16(NormAct):

@@ -299,9 +299,11 @@ def build_model(inputs, outputs, name="model", seed=7):
         def __init__(self):
             super().__init__(name, g.input_shape, seed)
             self.graph, self.out_nid = g, outputs.nid
-            for kind, layer, _, _ in g.nodes:
+            for kind, layer, _, attrs in g.nodes:
                 if layer is not None:
                     self._add(layer)
+                if kind == "conv_prelu":
+                    self._add(attrs["prelu"])            # the PReLU behind the convolution owns its slope, as the fp32 graph's node does
             # nodes computed from the network input alone (resized / concatenated / cropped / atanh'd input): data, no gradient flows to them
             self.const = {0}
             for i, (kind, layer, ins, _) in enumerate(g.nodes):
@@ -368,6 +370,14 @@ def build_model(inputs, outputs, name="model", seed=7):
                         vals[i], tape[i], pending[nj] = layer.forward_stats(vals[ins[0]], g.nodes[nj][1].norm == "instance")
                     else:
                         vals[i], tape[i] = layer.forward(vals[ins[0]])
+                elif kind == "conv_prelu":
+                    # fp32 NCHW frames -> bf16 NHWC: convolution + bias + PReLU in one launch (E.InitialConv9x9Bf16)
+                    vals[i], tape[i] = layer.forward_prelu(vals[ins[0]], self.ps[attrs["prelu"].prelu_name + "/alpha"], training)
+                elif kind == "gate_conv":
+                    # the fused gate (E.GateConvBf16): its first input is the constant frame node, its second the gated tensor
+                    vals[i], tape[i] = layer.forward(vals[ins[0]], vals[ins[1]])
+                elif kind == "to_f32":
+                    vals[i], tape[i] = E.from_bf16_nhwc(rt, vals[ins[0]]), None
                 elif kind == "gate":
                     a, m = vals[ins[0]], vals[ins[1]]
                     y = self.rt.empty(*m.shape)
@@ -435,6 +445,27 @@ def build_model(inputs, outputs, name="model", seed=7):
                     continue
                 src = ins[0]
                 need_dx = src not in self.const
+                if kind == "conv_prelu":
+                    # one or two bf16 gradients wait at the PReLU's output: its backward adds the pair in fp32 (no separate add launch)
+                    d1, d2 = d if isinstance(d, list) else (d, None)
+                    pn = g.nodes[i][3]["prelu"].prelu_name + "/alpha"
+                    layer.backward_prelu(tape[i], d1, d2, self.ps[pn], self.ps.grad(pn, which), which)
+                    continue
+                if isinstance(d, list):
+                    raise TypeError("two bf16 gradients meet at node %d (%s): no layer joins them there" % (i, kind))
+                if kind == "gate_conv":
+                    # the gradient already waiting at m (the Add of the same block) joins inside the gate's kernel; dm replaces it.  Where
+                    # a second one waits too (the long skip at initial/prelu's output), it stays for that node's backward
+                    m_nid = ins[1]
+                    prev = grads.get(m_nid)
+                    if isinstance(prev, list):
+                        grads[m_nid] = [prev[0], layer.backward(tape[i], d, which, dx_residual=prev[1])]
+                    else:
+                        grads[m_nid] = layer.backward(tape[i], d, which, dx_residual=prev)
+                    continue
+                if kind == "to_f32":
+                    self._acc(grads, src, E.to_bf16_nhwc(rt, d))
+                    continue
                 if kind == "gate":
                     a, m = tape[i]
                     da, dm = rt.empty(*a.shape), rt.empty(*m.shape)
@@ -484,6 +515,8 @@ def build_model(inputs, outputs, name="model", seed=7):
                     continue
                 if kind == "conv":
                     prev = grads.get(src)
+                    if isinstance(prev, list):
+                        raise TypeError("two bf16 gradients wait at node %d: a convolution joins one" % src)
                     dx = layer.backward(tape[i], d, need_dx, True, which, dx_residual=prev)
                     if need_dx:
                         grads[src] = dx
@@ -503,9 +536,15 @@ def build_model(inputs, outputs, name="model", seed=7):
             if nid in grads:
                 if grads[nid] is dx:
                     return
-                if grads[nid].dtype != E.torch.float32 or dx.dtype != E.torch.float32:
+                if not isinstance(grads[nid], list) and grads[nid].dtype == dx.dtype == E.torch.bfloat16:
+                    # two bf16 gradients: left side by side for a consumer that joins them in its own kernel (E.GateConvBf16's dx_residual,
+                    # E.InitialConv9x9Bf16.backward_prelu); vcg_axpby adds fp32 words
+                    grads[nid] = [grads[nid], dx]
+                    return
+                if isinstance(grads[nid], list) or grads[nid].dtype != E.torch.float32 or dx.dtype != E.torch.float32:
                     # vcg_axpby adds fp32 words; a bf16 gradient joins through a layer's dx_residual operand instead
-                    raise TypeError("two gradients meet at node %d in %s / %s: only fp32 gradients are accumulated here" % (nid, grads[nid].dtype, dx.dtype))
+                    have = "two bf16 tensors" if isinstance(grads[nid], list) else grads[nid].dtype
+                    raise TypeError("two gradients meet at node %d in %s / %s: only fp32 gradients are accumulated here" % (nid, have, dx.dtype))
                 # never write into a tensor another branch may still hold: accumulate into the new one
                 E.axpby(self.rt, grads[nid], dx, 1.0, 1.0)
             grads[nid] = dx
@@ -534,26 +573,79 @@ def make_upscaler_orig_functional(output_image_shape, kernel_size=5, filters=64,
     return build_model(upscaler_input, model, name="upscaler_orig_functional", seed=seed)
 
 
-def make_upscaler_attention(output_image_shape, kernel_size=5, filters=64, upscale_factor=4, res_block_num=16, norm="batch", seed=7):
+ATTENTION_BF16_SERVED = "the bf16 trunk of make_upscaler_attention (trunk_dtype='bf16') is instantiated for filters=64 on 3-channel (RGB) " \
+                        "frames, norm='batch', kernel_size 3 or 5 and upscale_factor 2 or 4 (any res_block_num); the bf16 tail " \
+                        "(trunk_dtype='bf16+tail') is not built for this generator; use trunk_dtype='fp32' for other shapes"
+
+
+def _attention_trunk_bf16(upscaler_input, kernel_size, res_block_num):
+    """initial/conv ... after_res/add of make_upscaler_attention on the bf16 layer classes, as nodes of the same graph (same layer names
+    and parameter order as the fp32 nodes), and the conversion back to fp32 NCHW behind it"""
+    g = upscaler_input.graph
+    node = lambda kind, layer, ins, **attrs: KTensor(g, g.add(kind, layer, [t.nid for t in ins], **attrs), 64)
+    conv = lambda t, name: node("conv", (E.Conv3x3Bf16 if kernel_size == 3 else E.Conv5x5Bf16)(name, 64, 64), [t])
+    # initial/conv + initial/prelu: one launch from the fp32 NCHW frames to bf16 NHWC; the slope is the parameter of its own layer, as in fp32
+    model = node("conv_prelu", E.InitialConv9x9Bf16("initial/conv", 3, 64, 9), [upscaler_input],
+                 prelu=E.NormAct("initial/prelu_op", 64, None, L.ACT_PRELU, prelu_name="initial/prelu"))
+    g.names.add("initial/prelu_op")
+    upsc_model = model
+    convs = []
+    for index in range(res_block_num):
+        n, gen = "res_block/" + str(index), model
+        model = node("gate_conv", E.GateConvBf16(n + "/attention", 3, 64, kernel_size), [upscaler_input, model])
+        g.names.add(n + "/attention_multiply")                   # the Multiply exists in Keras (its name is taken); the gate node computes it
+        model = conv(model, n + "/conv_pre")
+        convs.append(g.nodes[model.nid][1])
+        model = node("norm", E.NormActBf16(n + "/batch_norm_pre", 64, "batch", L.ACT_PRELU, prelu_name=n + "/prelu"), [model])
+        model = conv(model, n + "/conv_post")
+        convs.append(g.nodes[model.nid][1])
+        model = node("norm", E.NormActBf16(n + "/batch_norm_post", 64, "batch"), [model])
+        model = add([gen, model], name=n + "/final_add")          # fused into batch_norm_post's kernel
+    model = conv(model, "after_res/conv")
+    convs.append(g.nodes[model.nid][1])
+    model = node("norm", E.NormActBf16("after_res/batch_norm", 64, "batch"), [model])
+    model = add([upsc_model, model], name="after_res/add")
+    if kernel_size == 3 and len(convs) <= 48:
+        E.PackGroup3x3(convs)                                     # every 3x3 operand copy of the trunk in one launch per optimizer step
+    return node("to_f32", None, [model], name="after_res/to_f32")
+
+
+def make_upscaler_attention(output_image_shape, kernel_size=5, filters=64, upscale_factor=4, res_block_num=16, norm="batch", seed=7,
+                            trunk_dtype="fp32"):
     """make_upscaler_attention (model.py:299-328) -- the default generator of train_gan3.py (:55 'resnet-att', default -d 4) -- written
     block by block as the reference writes it.  Up-sampling block i resizes the input by 2**i (nearest and bilinear) for its attention
-    and adds Conv2DTranspose(kernel 2**(i+1)+1, strides 2**(i+1)) of atanh(0.99999 * input) (E.ConvTDilated for strides 4)."""
+    and adds Conv2DTranspose(kernel 2**(i+1)+1, strides 2**(i+1)) of atanh(0.99999 * input) (E.ConvTDilated for strides 4).
+
+    trunk_dtype='bf16' (make_upscaler_orig's keyword): initial/conv + initial/prelu, every residual_block_attention and after_res/conv +
+    batch_norm + add are stored bf16 NHWC, in training and in learning phase 0, on E.InitialConv9x9Bf16, E.GateConvBf16, E.Conv3x3Bf16 /
+    E.Conv5x5Bf16 and E.NormActBf16 as nodes of the same graph; master weights, gradients, statistics, moving averages, BN and PReLU
+    parameters stay fp32, layer names and parameter layouts are those of the fp32 model.  The up-sampling blocks and final/conv stay on
+    the fp32 layers.  ATTENTION_BF16_SERVED lists the shapes; others raise NotImplementedError."""
+    if trunk_dtype not in ("fp32", "bf16", "bf16+tail"):
+        raise ValueError(trunk_dtype)
+    if trunk_dtype == "bf16+tail" or (trunk_dtype == "bf16" and (filters != 64 or output_image_shape[2] != 3 or norm != "batch"
+                                                               or kernel_size not in (3, 5) or upscale_factor not in (2, 4))):
+        raise NotImplementedError(ATTENTION_BF16_SERVED)
     input_image_shape = (output_image_shape[0] // upscale_factor, output_image_shape[1] // upscale_factor, output_image_shape[2])
     upscale_times = int(math.log(upscale_factor, 2))
     upscaler_input = Input(shape=input_image_shape, name="initial/input")
-    model = conv2d(upscaler_input, filters, 9, 1, "same", name="initial/conv")
-    model = prelu(model, name="initial/prelu")
-    upsc_model = model
-    for index in range(res_block_num):
-        model = residual_block_attention(model, upscaler_input, kernel_size, filters, 1, name="res_block/" + str(index), norm=norm)
-    model = conv2d(model, filters, kernel_size, 1, "same", name="after_res/conv")
-    model = batch_norm(model, name="after_res/batch_norm", norm=norm)
-    model = add([upsc_model, model], name="after_res/add")
+    if trunk_dtype == "bf16":
+        model = _attention_trunk_bf16(upscaler_input, kernel_size, res_block_num)
+    else:
+        model = conv2d(upscaler_input, filters, 9, 1, "same", name="initial/conv")
+        model = prelu(model, name="initial/prelu")
+        upsc_model = model
+        for index in range(res_block_num):
+            model = residual_block_attention(model, upscaler_input, kernel_size, filters, 1, name="res_block/" + str(index), norm=norm)
+        model = conv2d(model, filters, kernel_size, 1, "same", name="after_res/conv")
+        model = batch_norm(model, name="after_res/batch_norm", norm=norm)
+        model = add([upsc_model, model], name="after_res/add")
     for index in range(upscale_times):
         scale = 2 ** (index + 1)
         model = upsampling_block_attention(model, upscaler_input, scale, kernel_size, 128, name="upscaling/" + str(index) + "/block")
     model = conv2d(model, 3, 9, 1, "same", activation="tanh", name="final/conv")
     net = build_model(upscaler_input, model, name="upscaler_attention", seed=seed)
+    net.trunk_dtype = trunk_dtype
     # what the bf16 inference engine recognises the topology by (not the name string), and its entry point
     net.attention_generator = {"kernel_size": kernel_size, "filters": filters, "upscale_factor": upscale_factor, "res_block_num": res_block_num,
                                "norm": norm, "channels": output_image_shape[2]}

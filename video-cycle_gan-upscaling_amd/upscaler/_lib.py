@@ -159,6 +159,7 @@ SIGNATURES = {
     "vcg_conv_in_gate_bf16_wfrag_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "vcg_pack_conv_in_gate_bf16": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "vcg_conv_in_gate_bf16_fwd": (c_int, [_D, _P, _P, _P, _P, _P, _P]),
+    "vcg_conv_in_gate_bf16_bwd": (c_int, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vcg_input_convt_add_bf16": (c_int, [_D, _P, _P, _P, _P, _P]),
     # generic bf16 NHWC convolution
     "vcg_conv_frag_bf16_bytes": (c_size_t, [c_int, c_int, c_int]),
