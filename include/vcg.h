@@ -435,6 +435,41 @@ int vcg_conv_in_gate_bf16_bwd(const vcg_conv_desc* d, const void* u, const void*
  * (k - s) / 2 = 0 in front), cout % 8 == 0 with the weights inside 64 KiB of LDS (cout <= 208 at s = 4); VCG_E_UNSUPPORTED otherwise.
  * No scratch memory. */
 int vcg_input_convt_add_bf16(const vcg_conv_desc* d, const void* x, const void* w_hwoi, const void* bias, void* y, hipStream_t stream);
+/* the same sum out of place: y_out = bf16(y_in + bias[c] + ...), same arithmetic and the same bits; y_in == y_out is the entry above.  What
+ * training needs: the LeakyReLU's output y_in is the mask of its backward and has to survive the Add of model.py:97. */
+int vcg_input_convt_add_bf16_to(const vcg_conv_desc* d, const void* x, const void* w_hwoi, const void* bias, const void* y_in, void* y_out,
+                                hipStream_t stream);
+/* The backward of that Add and of both branches' element-wise parts (what Keras derives from model.py:92-97), one pass over the gradient
+ * dY (bf16 NHWC [n][s h][s w][cout]) at the block's output; d, x as in the forward, y_act the LeakyReLU's output (the forward's y_in):
+ *   dz           = y_act > 0 ? dY : bf16(dY * slope)   bf16 NHWC, the gradient in front of the stage's LeakyReLU: element for element the
+ *                                                      rule of vcg_lrelu_bwd_bf16; must not be dY or y_act (VCG_E_UNSUPPORTED)
+ *   dbias_convt  [cout] or NULL = sum of the STORED dz (the rule of vcg_conv9x9_to3_bf16_dgrad_chsum): the stage's Conv2DTranspose bias
+ *   dbias_to_add [cout] or NULL = sum of dY
+ *   dw_hwoi      Keras' (s+1,s+1,cout,3): dw[ty][tx][co][ci] = sum over (n, iy, ix) of a[n,ci,iy,ix] * dY[n, s iy + ty, s ix + tx, co] with
+ *                a = atanh(0.99999 x) evaluated as the forward evaluates it and used as fp32; terms whose output index reaches s h or
+ *                s w are dropped (the row / column 'same' crops behind); fp32 products and sums
+ * All overwritten; deterministic (per-workgroup partial sums in ws, added up in a fixed order).  Served: what the forward serves with
+ * s * s * cout / 8 <= 256 (s = 4: cout <= 128); otherwise the query returns 0 and the call VCG_E_UNSUPPORTED; a workspace below the query:
+ * VCG_E_WORKSPACE.  No frames gradient: nothing trains in front of x.  No scratch memory.  (The size queries of the attention tail's
+ * entries end in _ws_bytes; their exact-size contract is checked in tests/test_abi_attention_tail_contract_gpu.py.) */
+size_t vcg_input_convt_add_bf16_bwd_ws_bytes(const vcg_conv_desc* d);
+int vcg_input_convt_add_bf16_bwd(const vcg_conv_desc* d, const void* x, const void* dY, const void* y_act, float slope, void* dz, float* dw_hwoi,
+                                 float* dbias_to_add, float* dbias_convt, void* ws, size_t ws_bytes, hipStream_t stream);
+/* vcg_conv_in_gate_bf16_bwd for the gates of upsampling_block_attention (what Keras derives from model.py:80-90): u is the 6-channel
+ * fp32 NCHW [n][6][h][w] Concatenate of the resized frames, wfrag = vcg_pack_conv_in_gate_bf16(cin 6), cout 64 or 128, 3x3 or 5x5, stride 1,
+ * pads k/2; same arithmetic (s with the forward's bits, dm = bf16(dy * s + dres) in fp32 with one rounding, da = bf16(dy * m * e * s^2),
+ * e = exp(-pre) clamped at 2^60), dres may be NULL (the bits of a dres of zeros).  Anything else, and dm == dres, dm == m or dm == da,
+ * returns VCG_E_UNSUPPORTED before any launch.  No workspace, no scratch memory. */
+int vcg_conv_in_gate_up_bf16_bwd(const vcg_conv_desc* d, const void* u, const void* wfrag, const void* bias, const void* m, const void* dy,
+                                 const void* dres, void* dm, void* da, hipStream_t stream);
+/* weight (+ bias) gradient of those gates' Conv2D(cout, k, 'same') on 6 channels (model.py:86) from u (fp32 NCHW [n][6][h][w]) and
+ * vcg_conv_in_gate_up_bf16_bwd's da (bf16 NHWC [n][h][w][cout]): vcg_conv3ch_bf16_wgrad's kernel once per 3-channel half of u (the bf16
+ * roundings the forward multiplies, packed from the planes of u in place: no fp32 copy of da, no 3-channel copy of u), dw fp32 in Keras'
+ * (k,k,6,cout) layout, dbias [cout] or NULL, overwritten; deterministic.  cout 64 or 128, k 3 or 5, even width; otherwise the query
+ * returns 0 and the call VCG_E_UNSUPPORTED (an odd width: run vcg_conv2d_wgrad on an fp32 copy of da). */
+size_t vcg_conv_in_gate_up_bf16_wgrad_ws_bytes(const vcg_conv_desc* d);
+int vcg_conv_in_gate_up_bf16_wgrad(const vcg_conv_desc* d, const float* u, const void* da, float* dw_hwio, float* dbias, void* ws, size_t ws_bytes,
+                                   vcg_stream_t stream);
 /* data gradient of such a first layer from the bf16 NHWC gradient dz [n][oh][ow][64] in front of its activation to the fp32 NCHW gradient
  * of the frames [n][3][h][w] (what the generator's backward consumes): the 3-channel result is computed as 12 (4x4 stride 2: four sub-pixel
  * phases x 3) or 3 of 64 virtual output channels of a 3x3 stride-1 convolution over dz on vcg_conv2d_nhwc_bf16_fwd and scattered.
@@ -508,6 +543,13 @@ int vcg_conv2d_bf16_wgrad(const vcg_conv_desc* d, const void* x, const void* dy,
  * VCG_E_WORKSPACE. */
 size_t vcg_conv9x9_to3_bf16_wgrad_workspace_bytes(const vcg_conv_desc* d);
 int vcg_conv9x9_to3_bf16_wgrad(const vcg_conv_desc* d, const void* x, const float* dz, float* dw_hwio, void* ws, size_t ws_bytes, hipStream_t stream);
+/* the same gradient on 128 input channels -- final/conv of make_upscaler_attention (upscaling/upscaler/model.py:326) -- under names of its
+ * own (the entry above keeps refusing cin = 128): x bf16 NHWC [n][h][w][128], dw (9,9,128,3); the contract of the 256 form (even width,
+ * dz fp32 NCHW rounded to bf16 as the operand, dw overwritten, deterministic).  The kernel is one channel half of the 256 form.  Other
+ * channel counts: the query returns 0 and the call VCG_E_UNSUPPORTED. */
+size_t vcg_conv9x9_c128to3_bf16_wgrad_ws_bytes(const vcg_conv_desc* d);
+int vcg_conv9x9_c128to3_bf16_wgrad(const vcg_conv_desc* d, const void* x, const float* dz, float* dw_hwio, void* ws, size_t ws_bytes,
+                                   hipStream_t stream);
 
 /* ---- generic bf16 NHWC Conv2D (any 3x3 / 4x4 / 5x5, stride 1-3, channels multiples of 32 / 16): the discriminators' layers in
  * the bf16 configs (upscaling/upscaler/model.py:839-871, 904-936; PatchGAN) and the generator's Conv2DTranspose gradients.

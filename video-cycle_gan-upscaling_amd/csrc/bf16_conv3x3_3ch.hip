@@ -1194,9 +1194,9 @@ int vcg_conv_in_gate_bf16_fwd(const vcg_conv_desc* d, const void* u, const void*
 // The gate's backward (model.py:33-36 differentiated): s = sigmoid(conv_kxk(u) + bias) is recomputed from the frames,
 //   dm = bf16(dy * s + dres)        (dres: a gradient joining at m, or NULL; fp32 sum, one rounding -- vcg_conv2d_nhwc_bf16_dgrad_add's rule)
 //   da = bf16(dy * m * s * (1 - s)) (the gradient in front of the gate convolution's bias: vcg_conv3ch_bf16_wgrad's dz)
-// in one launch, no workspace.  Served: cin 3, 3x3 / 5x5, stride 1, cout 64 (the residual blocks' gates).
-int vcg_conv_in_gate_bf16_bwd(const vcg_conv_desc* d, const void* u, const void* wfrag, const void* bias, const void* m, const void* dy,
-                              const void* dres, void* dm, void* da, hipStream_t stream) {
+// in one launch, no workspace.  Served: cin 3, 3x3 / 5x5, stride 1, cout 64 (the residual blocks' gates); up: cin 6, cout 64 or 128.
+static int gate_bwd(const vcg_conv_desc* d, bool up, const void* u, const void* wfrag, const void* bias, const void* m, const void* dy,
+                    const void* dres, void* dm, void* da, hipStream_t stream) {
     VCG_CHECK_PTR(d);
     VCG_CHECK_PTR(u);
     VCG_CHECK_PTR(wfrag);
@@ -1205,8 +1205,8 @@ int vcg_conv_in_gate_bf16_bwd(const vcg_conv_desc* d, const void* u, const void*
     VCG_CHECK_PTR(dm);
     VCG_CHECK_PTR(da);
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->oh != d->h || d->ow != d->w) return VCG_E_SHAPE;
-    if (d->cin != 3 || d->cout != 64 || d->kh != d->kw || (d->kh != 3 && d->kh != 5) || d->stride != 1 || d->pad_top != d->kh / 2 ||
-        d->pad_left != d->kw / 2)
+    const bool served = up ? d->cin == 6 && (d->cout == 64 || d->cout == 128) : d->cin == 3 && d->cout == 64;
+    if (!served || d->kh != d->kw || (d->kh != 3 && d->kh != 5) || d->stride != 1 || d->pad_top != d->kh / 2 || d->pad_left != d->kw / 2)
         return VCG_E_UNSUPPORTED;
     if (dm == dres || dm == m || dm == da) return VCG_E_UNSUPPORTED;          // m still feeds the block's Add; dres may be another branch's gradient
     if ((long)d->n * ceil_div(d->w, TC) * ceil_div(d->h, TR) > 0x7FFFFFFFl) return VCG_E_UNSUPPORTED;
@@ -1227,8 +1227,20 @@ int vcg_conv_in_gate_bf16_bwd(const vcg_conv_desc* d, const void* u, const void*
     p.tiles_x = ceil_div(d->ow, TC);
     p.tiles_y = ceil_div(d->oh, TR);
     p.total = p.n * p.tiles_x * p.tiles_y;
-    if (d->kh == 3) return launch_conv3ch<3, 1, 1, 1, GATE_BWD>(p, stream);
-    return launch_conv3ch<5, 2, 1, 1, GATE_BWD>(p, stream);
+    if (d->kh == 3) return up ? launch_conv3ch<3, 1, 1, 2, GATE_BWD>(p, stream) : launch_conv3ch<3, 1, 1, 1, GATE_BWD>(p, stream);
+    return up ? launch_conv3ch<5, 2, 1, 2, GATE_BWD>(p, stream) : launch_conv3ch<5, 2, 1, 1, GATE_BWD>(p, stream);
+}
+
+int vcg_conv_in_gate_bf16_bwd(const vcg_conv_desc* d, const void* u, const void* wfrag, const void* bias, const void* m, const void* dy,
+                              const void* dres, void* dm, void* da, hipStream_t stream) {
+    return gate_bwd(d, false, u, wfrag, bias, m, dy, dres, dm, da, stream);
+}
+
+// The same backward for the gates of upsampling_block_attention (model.py:80-90 differentiated): u is the 6-channel Concatenate of the two
+// resized frames -- NSRC = 2, the stacked halo tiles of the forward -- and cout is the up-sampling stage's 64 or 128.
+int vcg_conv_in_gate_up_bf16_bwd(const vcg_conv_desc* d, const void* u, const void* wfrag, const void* bias, const void* m, const void* dy,
+                                 const void* dres, void* dm, void* da, hipStream_t stream) {
+    return gate_bwd(d, true, u, wfrag, bias, m, dy, dres, dm, da, stream);
 }
 
 int vcg_conv9x9_from3_bf16_fwd(const vcg_conv_desc* d, const void* x, const void* wfrag, const void* bias, const void* prelu_alpha,

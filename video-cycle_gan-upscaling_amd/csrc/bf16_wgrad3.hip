@@ -218,7 +218,9 @@ __global__ __launch_bounds__(256, 2) void wgrad3_bf16_kernel(W3Params p) {
 // dW[tap][ci][co] (and db[co]) = sum over workgroups, in a fixed order, of the wave blocks.  block = 64 consecutive RAW dump elements x 16
 // record lanes (coalesced reads, eight records in flight per thread, fixed-order combine through LDS); the decoded (tap, ci, co) position
 // is only used for the single store.  The blocks past the weight dump sum the bias partials (two lane halves per record) the same way.
-template <int K>
+// CIN, CI0: the layer has CIN input channels of which this launch's 3-channel source is CI0 .. CI0 + 2 (the 6-channel gates of
+// upsampling_block_attention run the kernel above once per stacked source)
+template <int K, int CIN = 3, int CI0 = 0>
 __global__ __launch_bounds__(1024) void wgrad3_reduce_kernel(const float* __restrict__ ws, const float* __restrict__ wsb, int grid, int cout,
                                                              float* __restrict__ dw, float* __restrict__ db) {
     constexpr int T = K * K, NT = (T + 7) / 8, NTW = (NT + 1) / 2, WAVE_FLOATS = NTW * 16 * 64;
@@ -271,23 +273,24 @@ __global__ __launch_bounds__(1024) void wgrad3_reduce_kernel(const float* __rest
     const int l = off & 63, e = (off >> 6) & 15, j = off >> 10, mrow = wave & 1, chalf = wave >> 1;
     const int m = (e & 3) + 8 * (e >> 2) + 4 * (l >> 5), col = l & 31, tap = 8 * (chalf * NTW + j) + (col >> 2), ci = col & 3;
     const int co = cob * 64 + mrow * 32 + m;
-    if (tap < T && ci < 3) dw[(tap * 3 + ci) * cout + co] = t;
+    if (tap < T && ci < 3) dw[(tap * CIN + CI0 + ci) * cout + co] = t;
 }
 
-// fp32 NCHW frames [n][3][h][w] -> bf16 [n][h][w][4] (channel 3 = 0)
+// fp32 NCHW frames [n][3][h][w] -> bf16 [n][h][w][4] (channel 3 = 0); channels CI0 .. CI0 + 2 of [n][CIN][h][w]
+template <int CIN = 3, int CI0 = 0>
 __global__ void pack_frames3_bf16_kernel(const float* __restrict__ x, __bf16* __restrict__ out, int n, long hw) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n * hw) return;
     const long img = i / hw, px = i - img * hw;
     bf16x4 v;
-    v[0] = (__bf16)x[(img * 3 + 0) * hw + px];
-    v[1] = (__bf16)x[(img * 3 + 1) * hw + px];
-    v[2] = (__bf16)x[(img * 3 + 2) * hw + px];
+    v[0] = (__bf16)x[(img * CIN + CI0 + 0) * hw + px];
+    v[1] = (__bf16)x[(img * CIN + CI0 + 1) * hw + px];
+    v[2] = (__bf16)x[(img * CIN + CI0 + 2) * hw + px];
     v[3] = (__bf16)0.f;
     *(bf16x4*)(out + i * 4) = v;
 }
 
-template <int K, int S>
+template <int K, int S, int CIN = 3, int CI0 = 0>
 int launch_w3(const W3Params& p, float* dw, float* db, hipStream_t st) {
     using C = W3Cfg<K, S>;
     auto kern = wgrad3_bf16_kernel<K, S>;
@@ -295,7 +298,7 @@ int launch_w3(const W3Params& p, float* dw, float* db, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3(p.grid * p.co_blocks), dim3(256), C::NS * C::BUF, st, p);
     VCG_LAUNCH_CHECK();
     const int total = p.co_blocks * 4 * C::WAVE_FLOATS + p.cout;     // raw dump elements + bias channels
-    hipLaunchKernelGGL(wgrad3_reduce_kernel<K>, dim3(ceil_div(total, 64)), dim3(1024), 0, st, (const float*)p.ws, (const float*)p.wsb, p.grid, p.cout, dw, db);
+    hipLaunchKernelGGL((wgrad3_reduce_kernel<K, CIN, CI0>), dim3(ceil_div(total, 64)), dim3(1024), 0, st, (const float*)p.ws, (const float*)p.wsb, p.grid, p.cout, dw, db);
     VCG_LAUNCH_CHECK();
     return VCG_OK;
 }
@@ -310,6 +313,32 @@ bool w3_supported(const vcg_conv_desc* d) {
 size_t w3_wave_floats(int k) {
     const int T = k * k, NT = (T + 7) / 8, NTW = (NT + 1) / 2;
     return (size_t)NTW * 16 * 64;
+}
+
+// the launch parameters and the workspace's three parts: wave dumps, bias partials, the bf16 frames
+W3Params w3_params(const vcg_conv_desc* d, const void* dz, void* ws) {
+    W3Params p{};
+    const size_t cb = (size_t)(d->cout / 64);
+    p.ws = (float*)ws;
+    p.wsb = (float*)((char*)ws + align_up(cb * W3_GRID * 4 * w3_wave_floats(d->kh) * sizeof(float), 256));
+    unsigned char* xq = (unsigned char*)p.wsb + align_up(cb * W3_GRID * 128 * sizeof(float), 256);
+    xq += (256 - ((size_t)xq & 255)) & 255;
+    p.dz = (const unsigned char*)dz; p.xq = xq;
+    p.n = d->n; p.h = d->h; p.w_ = d->w; p.oh = d->oh; p.ow = d->ow; p.cout = d->cout; p.pt = d->pad_top; p.pl = d->pad_left;
+    p.tiles_x = ceil_div(d->ow, 32); p.tiles_y = ceil_div(d->oh, 4);
+    p.total = p.n * p.tiles_x * p.tiles_y;
+    p.grid = p.total < W3_GRID ? p.total : W3_GRID;
+    p.co_blocks = (int)cb;
+    return p;
+}
+
+// one 3-channel source (planes CI0 .. CI0 + 2) of a 6-channel gate input
+template <int K, int CI0>
+int up_gate_wgrad_source(W3Params& p, const float* u, float* dw, float* db, hipStream_t stream) {
+    const long hw = (long)p.h * p.w_, px = p.n * hw;
+    pack_frames3_bf16_kernel<6, CI0><<<(unsigned)((px + 255) / 256), 256, 0, stream>>>(u, (__bf16*)p.xq, p.n, hw);
+    VCG_LAUNCH_CHECK();
+    return launch_w3<K, 1, 6, CI0>(p, dw, db, stream);
 }
 
 }  // namespace
@@ -332,25 +361,54 @@ int vcg_conv3ch_bf16_wgrad(const vcg_conv_desc* d, const float* x, const void* d
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->oh <= 0 || d->ow <= 0) return VCG_E_SHAPE;
     if (!w3_supported(d)) return VCG_E_UNSUPPORTED;
     if (ws_bytes < vcg_conv3ch_bf16_wgrad_workspace_bytes(d)) return VCG_E_WORKSPACE;
-    W3Params p{};
-    const size_t cb = (size_t)(d->cout / 64);
-    p.ws = (float*)ws;
-    p.wsb = (float*)((char*)ws + align_up(cb * W3_GRID * 4 * w3_wave_floats(d->kh) * sizeof(float), 256));
-    unsigned char* xq = (unsigned char*)p.wsb + align_up(cb * W3_GRID * 128 * sizeof(float), 256);
-    xq += (256 - ((size_t)xq & 255)) & 255;
-    p.dz = (const unsigned char*)dz; p.xq = xq;
-    p.n = d->n; p.h = d->h; p.w_ = d->w; p.oh = d->oh; p.ow = d->ow; p.cout = d->cout; p.pt = d->pad_top; p.pl = d->pad_left;
-    p.tiles_x = ceil_div(d->ow, 32); p.tiles_y = ceil_div(d->oh, 4);
-    p.total = p.n * p.tiles_x * p.tiles_y;
-    p.grid = p.total < W3_GRID ? p.total : W3_GRID;
-    p.co_blocks = (int)cb;
+    const W3Params p = w3_params(d, dz, ws);
     const long px = (long)d->n * d->h * d->w;
-    pack_frames3_bf16_kernel<<<(unsigned)((px + 255) / 256), 256, 0, stream>>>(x, (__bf16*)xq, d->n, (long)d->h * d->w);
+    pack_frames3_bf16_kernel<<<(unsigned)((px + 255) / 256), 256, 0, stream>>>(x, (__bf16*)p.xq, d->n, (long)d->h * d->w);
     VCG_LAUNCH_CHECK();
     if (d->kh == 9) return launch_w3<9, 1>(p, dw_hwio, dbias, stream);
     if (d->kh == 5) return launch_w3<5, 1>(p, dw_hwio, dbias, stream);
     if (d->kh == 3) return launch_w3<3, 1>(p, dw_hwio, dbias, stream);
     return launch_w3<4, 2>(p, dw_hwio, dbias, stream);
+}
+
+// The gates of upsampling_block_attention (model.py:86): Conv2D(cout, k, 'same') on the 6-channel u = Concatenate[nearest, bilinear resize of
+// the frames].  The gradient is linear in the input channels: wgrad3_bf16_kernel<K, 1> runs once per 3-channel source -- its bf16 pixels are
+// packed from planes 3 src .. 3 src + 2 of u's 6 into the workspace's one frame slot, in stream order -- and the reduction writes rows
+// 3 src .. 3 src + 2 of the (k,k,6,cout) kernel.  The bias sum rides along with the first source.
+static vcg_conv_desc up_gate_as_3ch(const vcg_conv_desc* d) {
+    vcg_conv_desc d3 = *d;
+    d3.cin = 3;
+    return d3;
+}
+
+static bool up_gate_wgrad_shape(const vcg_conv_desc* d) {
+    return d->cin == 6 && (d->cout == 64 || d->cout == 128) && d->kh == d->kw && (d->kh == 3 || d->kh == 5) && d->stride == 1 &&
+           d->pad_top == d->kh / 2 && d->pad_left == d->kw / 2 && d->oh == d->h && d->ow == d->w;
+}
+
+size_t vcg_conv_in_gate_up_bf16_wgrad_ws_bytes(const vcg_conv_desc* d) {
+    if (d == nullptr || d->n <= 0 || d->h <= 0 || d->w <= 0 || !up_gate_wgrad_shape(d)) return 0;
+    const vcg_conv_desc d3 = up_gate_as_3ch(d);
+    return vcg_conv3ch_bf16_wgrad_workspace_bytes(&d3);
+}
+
+int vcg_conv_in_gate_up_bf16_wgrad(const vcg_conv_desc* d, const float* u, const void* da, float* dw_hwio, float* dbias, void* ws, size_t ws_bytes,
+                                   vcg_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    VCG_CHECK_PTR(d); VCG_CHECK_PTR(u); VCG_CHECK_PTR(da); VCG_CHECK_PTR(dw_hwio); VCG_CHECK_PTR(ws);
+    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->oh <= 0 || d->ow <= 0) return VCG_E_SHAPE;
+    const vcg_conv_desc d3 = up_gate_as_3ch(d);
+    if (!up_gate_wgrad_shape(d) || !w3_supported(&d3)) return VCG_E_UNSUPPORTED;
+    if (ws_bytes < vcg_conv_in_gate_up_bf16_wgrad_ws_bytes(d)) return VCG_E_WORKSPACE;
+    W3Params p = w3_params(&d3, da, ws);
+    if (d->kh == 3) {
+        if (int e = up_gate_wgrad_source<3, 0>(p, u, dw_hwio, dbias, stream)) return e;
+        p.wsb = nullptr;
+        return up_gate_wgrad_source<3, 3>(p, u, dw_hwio, nullptr, stream);
+    }
+    if (int e = up_gate_wgrad_source<5, 0>(p, u, dw_hwio, dbias, stream)) return e;
+    p.wsb = nullptr;
+    return up_gate_wgrad_source<5, 3>(p, u, dw_hwio, nullptr, stream);
 }
 
 }  // extern "C"

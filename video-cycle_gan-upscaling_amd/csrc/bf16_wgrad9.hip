@@ -43,6 +43,11 @@ static_assert(W9_WAVE_FLOATS % 64 == 0, "wgrad9 reduce: 64 raw elements per bloc
 template <int CIN> struct W9Cfg;
 template <> struct W9Cfg<256> { static constexpr int MT = 4, PX = 256, SRC_PX = 512, HALVES = 2, GRID = 128; };
 template <> struct W9Cfg<64> { static constexpr int MT = 2, PX = 128, SRC_PX = 128, HALVES = 1, GRID = 256; };
+// 128 channels (final/conv of make_upscaler_attention, model.py:326) are ONE of the 256 form's halves: the same 256-byte LDS pixels, four
+// row tiles per wave and 36-KiB stages, with the whole pixel in memory.  GRID: the three stages (108 KiB) and 192 accumulator registers allow
+// one workgroup per CU, as in the 256 form, whose 2 x 128 workgroups fill the 256 CUs once -- 256 workgroups here do the same, and the
+// dumps (GRID x MT wave blocks) have the 256 form's size.
+template <> struct W9Cfg<128> { static constexpr int MT = 4, PX = 256, SRC_PX = 256, HALVES = 1, GRID = 256; };
 
 template <int CIN> struct W9 : W9Cfg<CIN> {
     using C = W9Cfg<CIN>;
@@ -317,6 +322,21 @@ size_t vcg_conv9x9_to3_bf16_wgrad_workspace_bytes(const vcg_conv_desc* d) {
     if (d == nullptr || d->n <= 0 || d->h <= 0 || d->w <= 0 || (d->cin != 256 && d->cin != 64)) return 0;
     const size_t dumps = d->cin == 64 ? W9<64>::DUMP_FLOATS : W9<256>::DUMP_FLOATS;
     return dumps * sizeof(float) + (size_t)d->n * d->h * d->w * 8 + 256;
+}
+
+// final/conv of make_upscaler_attention: 128 input channels, under names of its own (the entry points above keep refusing cin = 128)
+size_t vcg_conv9x9_c128to3_bf16_wgrad_ws_bytes(const vcg_conv_desc* d) {
+    if (d == nullptr || d->n <= 0 || d->h <= 0 || d->w <= 0 || d->cin != 128) return 0;
+    return W9<128>::DUMP_FLOATS * sizeof(float) + (size_t)d->n * d->h * d->w * 8 + 256;
+}
+
+int vcg_conv9x9_c128to3_bf16_wgrad(const vcg_conv_desc* d, const void* x, const float* dz, float* dw_hwio, void* ws, size_t ws_bytes, hipStream_t stream) {
+    VCG_CHECK_PTR(d); VCG_CHECK_PTR(x); VCG_CHECK_PTR(dz); VCG_CHECK_PTR(dw_hwio); VCG_CHECK_PTR(ws);
+    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->oh != d->h || d->ow != d->w) return VCG_E_SHAPE;
+    if (d->cin != 128 || d->cout != 3 || d->kh != 9 || d->kw != 9 || d->stride != 1 || d->pad_top != 4 || d->pad_left != 4) return VCG_E_UNSUPPORTED;
+    if (d->w % 2 || (long)d->h * d->w * d->cin * 2 > 0xFFFFFFE0l) return VCG_E_UNSUPPORTED;     // dz pairs must not straddle rows; one image per buffer descriptor
+    if (ws_bytes < vcg_conv9x9_c128to3_bf16_wgrad_ws_bytes(d)) return VCG_E_WORKSPACE;
+    return wgrad9_launch<128>(d, x, dz, dw_hwio, ws, stream);
 }
 
 int vcg_conv9x9_to3_bf16_wgrad(const vcg_conv_desc* d, const void* x, const float* dz, float* dw_hwio, void* ws, size_t ws_bytes, hipStream_t stream) {

@@ -958,21 +958,22 @@ def conv_nhwc_bf16_wgrad(layer, d, x, dy, which, tag):
                 "vcg_conv2d_nhwc_bf16_wgrad[%s]" % layer.name)
 
 
-def conv3ch_bf16_wgrad(layer, d, x, dz, which, tag, need=None):
+def conv3ch_bf16_wgrad(layer, d, x, dz, which, tag, need=None, entry="vcg_conv3ch_bf16_wgrad", query="vcg_conv3ch_bf16_wgrad_workspace_bytes"):
     """weight / bias gradient of a layer on the 3-channel fp32 NCHW frames x from the bf16 NHWC gradient dz: vcg_conv3ch_bf16_wgrad (frames
     and gradient as bf16 MFMA operands), or at odd widths -- the kernel then asks for no workspace -- the fp32 kernel on an fp32 NCHW copy
-    of dz, which is returned (None otherwise).  need: the workspace size where the caller has already asked for it."""
+    of dz, which is returned (None otherwise).  need: the workspace size where the caller has already asked for it.  entry: the entry point
+    and its size query, of the same contract for another input (vcg_conv_in_gate_up_bf16_wgrad: the 6-channel input of the up-sampling gates)."""
     rt = layer.rt
-    need = rt.lib.vcg_conv3ch_bf16_wgrad_workspace_bytes(ctypes.byref(d)) if need is None else need
+    need = getattr(rt.lib, query)(ctypes.byref(d)) if need is None else need
     if not need:
         dz32 = from_bf16_nhwc(rt, dz)
         layer._wgrad_fp32(d, x, dz32, which, True, tag)
         return dz32
     ws, wsn = rt.workspace(need)
     with Timed(rt, tag and tag + "_wgrad"):
-        L.check(rt.lib.vcg_conv3ch_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dz.data_ptr(), layer.ps.grad(layer.name + "/kernel", which).data_ptr(),
-                                              layer.ps.grad(layer.name + "/bias", which).data_ptr(), ws, wsn, rt.stream),
-                "vcg_conv3ch_bf16_wgrad[%s]" % layer.name)
+        L.check(getattr(rt.lib, entry)(ctypes.byref(d), x.data_ptr(), dz.data_ptr(), layer.ps.grad(layer.name + "/kernel", which).data_ptr(),
+                                       layer.ps.grad(layer.name + "/bias", which).data_ptr(), ws, wsn, rt.stream),
+                "%s[%s]" % (entry, layer.name))
     return None
 
 
@@ -1327,6 +1328,72 @@ class ConvT3x3Bf16(ConvTBf16):
         return y, (x, y, d)
 
 
+class UpConvTBf16(ConvTBf16):
+    """conv_transp of upsampling_block_attention (model.py:91-92) on bf16 NHWC: Conv2DTranspose(128, k, strides 2) + bias + LeakyReLU(0.2)
+    on the 64 (first block) or 128 (second block) gated channels, k 3 or 5 -- ConvTBf16's kernels at shapes of its own.  The Add of
+    to_add_input follows (ToAddInputBf16): its backward hands this layer dz, the gradient in front of the LeakyReLU, and the channel sums
+    of dz, so backward is ConvTBf16's with dz_channel_sums."""
+
+    def __init__(self, name, cin, cout, k, act=L.ACT_LRELU, alpha=0.2):
+        if k not in (3, 5) or cin not in (64, 128) or cout != 128 or act != L.ACT_LRELU:
+            raise NotImplementedError("the bf16 transposed convolution of the attention generator's up-sampling blocks serves 3x3 / 5x5, 64 or 128 "
+                                      "-> 128 channels with LeakyReLU")
+        ConvT2D.__init__(self, name, cin, cout, k, act, alpha)
+        self._pk = PackedOperand(self._pack, self)
+
+
+class ToAddInputBf16(ConvT2D):
+    """to_add_input and add_input of upsampling_block_attention (model.py:94-97) on the bf16 path: y = bf16(y_act + bias +
+    Conv2DTranspose(cout, s+1, strides s, 'same')(atanh(0.99999 frames))) with the atanh, the transposed convolution on three channels and
+    the Add in one launch (vcg_input_convt_add_bf16_to; in learning phase 0 in place on y_act, vcg_input_convt_add_bf16).  Owns
+    to_add_input_conv_transp/kernel (s+1,s+1,cout,3) and /bias under the fp32 model's names, used as fp32.  backward
+    (vcg_input_convt_add_bf16_bwd) reads the gradient dY at the block's output once and returns dz -- the gradient in front of the
+    LeakyReLU that produced y_act -- with its channel sums (the transposed convolution's bias gradient) for UpConvTBf16.backward, and
+    leaves this layer's own weight and bias gradient.  The frames are the network input: no gradient goes to them."""
+
+    def __init__(self, name, cin, cout, stride, slope=0.2):
+        if cin != 3 or stride not in (2, 4) or cout % 8 or stride * stride * cout // 8 > 256:
+            raise NotImplementedError("the bf16 to_add_input is instantiated for 3 input channels, strides 2 or 4 (kernel strides + 1) and "
+                                      "8m channels, strides^2 m <= 256")
+        super().__init__(name, cin, cout, stride + 1, L.ACT_NONE, 0.0)
+        self.stride, self.slope = stride, slope
+
+    def desc(self, n, h, w):
+        s = self.stride
+        return L.ConvDesc(n, 3, h, w, self.cout, s * h, s * w, s + 1, s + 1, s, 0, 0)
+
+    def forward(self, x, y_act, training=True, tag=None):
+        """x: the fp32 NCHW frames [n,3,h,w]; y_act: bf16 NHWC [n,s h,s w,cout], kept (training) or overwritten with the sum"""
+        rt = self.rt
+        n, c, h, w = x.shape
+        d = self.desc(n, h, w)
+        if c != 3 or y_act.dtype != torch.bfloat16 or tuple(y_act.shape) != (n, d.oh, d.ow, self.cout):
+            raise TypeError("ToAddInputBf16[%s]: x fp32 NCHW frames [n,3,h,w], y_act bf16 NHWC [n,%dh,%dw,%d]" % (self.name, self.stride, self.stride, self.cout))
+        y = torch.empty_like(y_act) if training else y_act
+        with Timed(rt, tag):
+            L.check(rt.lib.vcg_input_convt_add_bf16_to(ctypes.byref(d), x.data_ptr(), self.ps[self.name + "/kernel"].data_ptr(),
+                                                       self.ps[self.name + "/bias"].data_ptr(), y_act.data_ptr(), y.data_ptr(), rt.stream),
+                    "vcg_input_convt_add_bf16_to[%s]" % self.name)
+        return y, (x, y_act if training else None, d)
+
+    def backward(self, ctx, dy, which=0, tag=None):
+        """dy: bf16 NHWC gradient at the block's output.  Returns (dz, (channel sums of dz, 1)): UpConvTBf16.backward's dz and dz_channel_sums"""
+        rt = self.rt
+        x, y_act, d = ctx
+        if y_act is None:
+            raise RuntimeError("ToAddInputBf16[%s]: the forward pass ran in learning phase 0 and kept no activation" % self.name)
+        if dy.dtype != torch.bfloat16 or tuple(dy.shape) != tuple(y_act.shape):
+            raise TypeError("ToAddInputBf16[%s]: the gradient is a bf16 NHWC tensor of the output's shape" % self.name)
+        dz, sums = torch.empty_like(dy), rt.empty(self.cout)
+        ws, wsn = rt.workspace(rt.lib.vcg_input_convt_add_bf16_bwd_ws_bytes(ctypes.byref(d)))
+        with Timed(rt, tag and tag + "_bwd"):
+            L.check(rt.lib.vcg_input_convt_add_bf16_bwd(ctypes.byref(d), x.data_ptr(), dy.data_ptr(), y_act.data_ptr(), float(self.slope), dz.data_ptr(),
+                                                        self.ps.grad(self.name + "/kernel", which).data_ptr(),
+                                                        self.ps.grad(self.name + "/bias", which).data_ptr(), sums.data_ptr(), ws, wsn, rt.stream),
+                    "vcg_input_convt_add_bf16_bwd[%s]" % self.name)
+        return dz, (sums, 1)
+
+
 class Conv9x9To3Bf16(Conv2D):
     """Conv2D(3, 9, 'same') + tanh on a bf16 NHWC input with CIN channels, fp32 NCHW output: final/conv (model.py:290-291) on 256 channels
     and head/conv of make_generator_cyclegan on 64.  Forward on the entry point FWD over the operand PACK_FWD lays out; data gradient on
@@ -1334,6 +1401,7 @@ class Conv9x9To3Bf16(Conv2D):
     the first layer with the roles swapped, once per 64 channels); weight gradient on vcg_conv9x9_to3_bf16_wgrad (even widths; odd ones take
     the fp32 kernel on an fp32 NCHW copy of the input).  INPUT_ACT: whether backward serves input_lrelu_slope and want_channel_sums."""
     CIN = FWD = PACK_FWD = DGRAD_PACK_BYTES = REFUSAL = DGRAD_LABEL = INPUT_ACT = None
+    WGRAD, WGRAD_QUERY = "vcg_conv9x9_to3_bf16_wgrad", "vcg_conv9x9_to3_bf16_wgrad_workspace_bytes"           # the weight gradient's entry point and its size query
 
     def __init__(self, name, cin, cout, k, act=L.ACT_TANH):
         if cin != self.CIN or cout != 3 or k != 9:
@@ -1375,11 +1443,11 @@ class Conv9x9To3Bf16(Conv2D):
             dy = act_bwd_bias(self, y, dy, d, param_grads, which)
         if param_grads and d.w % 2 == 0:
             # bf16 weight gradient straight from the bf16 NHWC input (transposed LDS reads); dz enters as a bf16 MFMA operand
-            ws, wsn = rt.workspace(max(rt.lib.vcg_conv9x9_to3_bf16_wgrad_workspace_bytes(ctypes.byref(d)),
+            ws, wsn = rt.workspace(max(getattr(rt.lib, self.WGRAD_QUERY)(ctypes.byref(d)),
                                        rt.lib.vcg_channel_sum_workspace_bytes(n, 3, d.oh * d.ow)))
             with Timed(rt, tag and tag + "_wgrad"):
-                L.check(rt.lib.vcg_conv9x9_to3_bf16_wgrad(ctypes.byref(d), x.data_ptr(), dy.data_ptr(), self.ps.grad(self.name + "/kernel", which).data_ptr(),
-                                                          ws, wsn, rt.stream), "vcg_conv9x9_to3_bf16_wgrad[%s]" % self.name)
+                L.check(getattr(rt.lib, self.WGRAD)(ctypes.byref(d), x.data_ptr(), dy.data_ptr(), self.ps.grad(self.name + "/kernel", which).data_ptr(),
+                                                    ws, wsn, rt.stream), "%s[%s]" % (self.WGRAD, self.name))
             if not db_done:
                 L.check(rt.lib.vcg_channel_sum(dy.data_ptr(), n, 3, d.oh * d.ow, self.ps.grad(self.name + "/bias", which).data_ptr(), ws, wsn,
                                                rt.stream), "vcg_channel_sum[%s]" % self.name)
@@ -1418,6 +1486,16 @@ class HeadConv9x9C64Bf16(Conv9x9To3Bf16):
     REFUSAL, DGRAD_LABEL = "the bf16 head convolution is instantiated for 9x9, 64 -> 3 channels", "vcg_conv9x9_to3_bf16_dgrad[%(name)s]"
 
 
+class FinalConv9x9C128Bf16(Conv9x9To3Bf16):
+    """final/conv of make_upscaler_attention (model.py:326) behind the 128-channel up-sampling blocks, whose last layer is the Add of
+    to_add_input: no activation mask in the data gradient.  Forward on vcg_conv9x9_to3_bf16_fwd (cin 128), weight gradient on
+    vcg_conv9x9_c128to3_bf16_wgrad."""
+    CIN, FWD, DGRAD_PACK_BYTES, INPUT_ACT = 128, "vcg_conv9x9_to3_bf16_fwd", 2 * L.FIRST9X9_WFRAG_BYTES, False
+    PACK_FWD = staticmethod(lambda rt, w, out=None: pack_conv9x9_to3_bf16(rt, w, 128, out))
+    REFUSAL, DGRAD_LABEL = "the bf16 final convolution of the attention generator is instantiated for 9x9, 128 -> 3 channels", "vcg_conv9x9_to3_bf16_dgrad[%(name)s]"
+    WGRAD, WGRAD_QUERY = "vcg_conv9x9_c128to3_bf16_wgrad", "vcg_conv9x9_c128to3_bf16_wgrad_ws_bytes"
+
+
 
 class StemConv9x9Bf16(InitialConv9x9Bf16):
     """stem/conv of make_generator_cyclegan as a graph node: Conv2D(64, 9, 'same') + bias from the fp32 NCHW frames to bf16 NHWC
@@ -1454,18 +1532,21 @@ class GateConvBf16(Conv2D):
     backward: vcg_conv_in_gate_bf16_bwd recomputes the sigmoid from the frames and writes dm (with the gradient joining at m added before
     the one rounding) and da, from which vcg_conv3ch_bf16_wgrad takes the gate's weight / bias gradient (odd widths: the fp32 kernel on an
     fp32 NCHW copy of da).  The attention tensor is never stored; the context is (u, m).  Declares the Conv2D's parameters under the
-    fp32 model's names (res_block/i/attention/kernel, /bias).  The frames are the network input: no gradient goes to u."""
+    fp32 model's names (res_block/i/attention/kernel, /bias).  The frames are the network input: no gradient goes to u.
+    CIN, COUTS: the shapes the class serves; BWD, WGRAD, WGRAD_QUERY: the entry points of its backward."""
+    CIN, COUTS, BWD, WGRAD, WGRAD_QUERY = 3, (64,), "vcg_conv_in_gate_bf16_bwd", "vcg_conv3ch_bf16_wgrad", "vcg_conv3ch_bf16_wgrad_workspace_bytes"
+    REFUSAL = "the bf16 gate is instantiated for 3x3 / 5x5, 3 -> 64 channels"
 
     def __init__(self, name, cin=3, cout=64, k=3):
-        if cin != 3 or cout != 64 or k not in (3, 5):
-            raise NotImplementedError("the bf16 gate is instantiated for 3x3 / 5x5, 3 -> 64 channels")
+        if cin != self.CIN or cout not in self.COUTS or k not in (3, 5):
+            raise NotImplementedError(self.REFUSAL)
         super().__init__(name, cin, cout, k)
-        self._pk = PackedOperand(lambda out: pack_conv_in_gate_bf16(self.rt, self.ps[self.name + "/kernel"], 3, k, k, 64, out), self)
+        self._pk = PackedOperand(lambda out: pack_conv_in_gate_bf16(self.rt, self.ps[self.name + "/kernel"], cin, k, k, cout, out), self)
 
     def _check(self, u, m):
         n, c, h, w = u.shape
-        if c != 3 or m.dtype != torch.bfloat16 or tuple(m.shape) != (n, h, w, self.cout):
-            raise TypeError("GateConvBf16[%s]: u fp32 NCHW frames [n,3,h,w], m bf16 NHWC [n,h,w,%d]" % (self.name, self.cout))
+        if c != self.CIN or m.dtype != torch.bfloat16 or tuple(m.shape) != (n, h, w, self.cout):
+            raise TypeError("%s[%s]: u fp32 NCHW [n,%d,h,w], m bf16 NHWC [n,h,w,%d]" % (type(self).__name__, self.name, self.CIN, self.cout))
         return self.desc(n, h, w)
 
     def forward(self, u, m, tag=None):
@@ -1484,14 +1565,26 @@ class GateConvBf16(Conv2D):
         d = self._check(u, m)
         for t in (dy, dx_residual):
             if t is not None and (t.dtype != torch.bfloat16 or tuple(t.shape) != tuple(m.shape)):
-                raise TypeError("GateConvBf16[%s]: gradients are bf16 NHWC tensors of m's shape" % self.name)
+                raise TypeError("%s[%s]: gradients are bf16 NHWC tensors of m's shape" % (type(self).__name__, self.name))
         dm, da = torch.empty_like(m), torch.empty_like(m)
         with Timed(rt, tag and tag + "_bwd"):
-            L.check(rt.lib.vcg_conv_in_gate_bf16_bwd(ctypes.byref(d), u.data_ptr(), self._pk.get().data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
-                                                     m.data_ptr(), dy.data_ptr(), _ptr(dx_residual), dm.data_ptr(), da.data_ptr(), rt.stream),
-                    "vcg_conv_in_gate_bf16_bwd[%s]" % self.name)
-        conv3ch_bf16_wgrad(self, d, u, da, which, tag)
+            L.check(getattr(rt.lib, self.BWD)(ctypes.byref(d), u.data_ptr(), self._pk.get().data_ptr(), self.ps[self.name + "/bias"].data_ptr(),
+                                              m.data_ptr(), dy.data_ptr(), _ptr(dx_residual), dm.data_ptr(), da.data_ptr(), rt.stream),
+                    "%s[%s]" % (self.BWD, self.name))
+        conv3ch_bf16_wgrad(self, d, u, da, which, tag, entry=self.WGRAD, query=self.WGRAD_QUERY)
         return dm
+
+
+class UpGateConvBf16(GateConvBf16):
+    """The gate of upsampling_block_attention (model.py:80-90) on bf16 NHWC: u is the fp32 NCHW Concatenate of the nearest and the bilinear
+    resize of the frames (6 channels, data only), cout the 64 or 128 channels of the tensor it gates.  Forward on the same
+    vcg_conv_in_gate_bf16_fwd; backward on vcg_conv_in_gate_up_bf16_bwd and vcg_conv_in_gate_up_bf16_wgrad (odd widths: the fp32 kernel on
+    an fp32 NCHW copy of da).  Parameters under the fp32 model's names (upscaling/i/block/attention/kernel, /bias)."""
+    CIN, COUTS, BWD, WGRAD, WGRAD_QUERY = 6, (64, 128), "vcg_conv_in_gate_up_bf16_bwd", "vcg_conv_in_gate_up_bf16_wgrad", "vcg_conv_in_gate_up_bf16_wgrad_ws_bytes"
+    REFUSAL = "the bf16 up-sampling gate is instantiated for 3x3 / 5x5, 6 -> 64 or 128 channels"
+
+    def __init__(self, name, cin=6, cout=128, k=3):
+        super().__init__(name, cin, cout, k)
 
 
 class NormActBf16(NormAct):

@@ -62,7 +62,7 @@ class _Graph:
         if kind == "crop":
             (t, b), (l, r) = attrs["cropping"]
             return (h - t - b, w - l - r)
-        if kind == "gate":
+        if kind in ("gate", "add_input"):
             return self.hw[ins[1]]
         for j in ins[1:]:
             if self.hw[j] != (h, w) and kind in ("norm", "concat"):
@@ -334,7 +334,7 @@ def build_model(inputs, outputs, name="model", seed=7):
                     shapes[i] = (oh, ow)
                 elif kind == "convt":
                     shapes[i] = (g.nodes[i][3].get("stride", 2) * ih, g.nodes[i][3].get("stride", 2) * iw)
-                elif kind == "gate":
+                elif kind in ("gate", "add_input"):
                     shapes[i] = shapes[ins[1]]
                 elif kind == "resize":
                     shapes[i] = (ih * g.nodes[i][3]["factor"], iw * g.nodes[i][3]["factor"])
@@ -376,6 +376,9 @@ def build_model(inputs, outputs, name="model", seed=7):
                 elif kind == "gate_conv":
                     # the fused gate (E.GateConvBf16): its first input is the constant frame node, its second the gated tensor
                     vals[i], tape[i] = layer.forward(vals[ins[0]], vals[ins[1]])
+                elif kind == "add_input":
+                    # to_add_input + the block's Add (E.ToAddInputBf16): the frames and the LeakyReLU's output, kept in training for its mask
+                    vals[i], tape[i] = layer.forward(vals[ins[0]], vals[ins[1]], training)
                 elif kind == "to_f32":
                     vals[i], tape[i] = E.from_bf16_nhwc(rt, vals[ins[0]]), None
                 elif kind == "gate":
@@ -463,6 +466,13 @@ def build_model(inputs, outputs, name="model", seed=7):
                     else:
                         grads[m_nid] = layer.backward(tape[i], d, which, dx_residual=prev)
                     continue
+                if kind == "add_input":
+                    # one pass over the gradient at the block's output: this layer's own gradients, and for the transposed convolution in
+                    # front of it the gradient in front of its LeakyReLU together with that gradient's channel sums
+                    if ins[1] in grads:
+                        raise TypeError("a second gradient waits at node %d: add_input is its only consumer" % ins[1])
+                    grads[ins[1]] = layer.backward(tape[i], d, which)
+                    continue
                 if kind == "to_f32":
                     self._acc(grads, src, E.to_bf16_nhwc(rt, d))
                     continue
@@ -520,6 +530,11 @@ def build_model(inputs, outputs, name="model", seed=7):
                     dx = layer.backward(tape[i], d, need_dx, True, which, dx_residual=prev)
                     if need_dx:
                         grads[src] = dx
+                elif kind == "convt" and isinstance(d, tuple):
+                    dz, sums = d                                  # from the add_input node behind an E.UpConvTBf16
+                    dx = layer.backward(tape[i], dz, need_dx, True, which, dz_channel_sums=sums)
+                    if need_dx:
+                        self._acc(grads, src, dx)
                 elif kind == "convt":
                     dx = layer.backward(tape[i], d, need_dx, True, which)
                     if need_dx:
@@ -573,14 +588,15 @@ def make_upscaler_orig_functional(output_image_shape, kernel_size=5, filters=64,
     return build_model(upscaler_input, model, name="upscaler_orig_functional", seed=seed)
 
 
-ATTENTION_BF16_SERVED = "the bf16 trunk of make_upscaler_attention (trunk_dtype='bf16') is instantiated for filters=64 on 3-channel (RGB) " \
-                        "frames, norm='batch', kernel_size 3 or 5 and upscale_factor 2 or 4 (any res_block_num); the bf16 tail " \
-                        "(trunk_dtype='bf16+tail') is not built for this generator; use trunk_dtype='fp32' for other shapes"
+ATTENTION_BF16_SERVED = "the bf16 trunk of make_upscaler_attention (trunk_dtype='bf16') and its bf16 tail (tail_dtype='bf16', which needs the " \
+                        "bf16 trunk) are instantiated for filters=64 on 3-channel (RGB) frames, norm='batch', kernel_size 3 or 5 and " \
+                        "upscale_factor 2 or 4 (any res_block_num); trunk_dtype='bf16+tail' is not a spelling of this generator: the bf16 tail " \
+                        "is tail_dtype='bf16'; use trunk_dtype='fp32' for other shapes"
 
 
-def _attention_trunk_bf16(upscaler_input, kernel_size, res_block_num):
+def _attention_trunk_bf16(upscaler_input, kernel_size, res_block_num, to_f32=True):
     """initial/conv ... after_res/add of make_upscaler_attention on the bf16 layer classes, as nodes of the same graph (same layer names
-    and parameter order as the fp32 nodes), and the conversion back to fp32 NCHW behind it"""
+    and parameter order as the fp32 nodes), and (to_f32) the conversion back to fp32 NCHW behind it"""
     g = upscaler_input.graph
     node = lambda kind, layer, ins, **attrs: KTensor(g, g.add(kind, layer, [t.nid for t in ins], **attrs), 64)
     conv = lambda t, name: node("conv", (E.Conv3x3Bf16 if kernel_size == 3 else E.Conv5x5Bf16)(name, 64, 64), [t])
@@ -607,11 +623,33 @@ def _attention_trunk_bf16(upscaler_input, kernel_size, res_block_num):
     model = add([upsc_model, model], name="after_res/add")
     if kernel_size == 3 and len(convs) <= 48:
         E.PackGroup3x3(convs)                                     # every 3x3 operand copy of the trunk in one launch per optimizer step
-    return node("to_f32", None, [model], name="after_res/to_f32")
+    return node("to_f32", None, [model], name="after_res/to_f32") if to_f32 else model
+
+
+def _attention_tail_bf16(model, upscaler_input, kernel_size, upscale_times):
+    """the up-sampling blocks and final/conv of make_upscaler_attention on the bf16 layer classes, as nodes of the same graph behind the
+    bf16 after_res/add (same layer names and parameter order as the fp32 nodes).  Per block: the resize / concatenate nodes of the gate's
+    6-channel input stay fp32 data nodes; E.UpGateConvBf16 is attention + sigmoid + Multiply, E.UpConvTBf16 conv_transp + LeakyReLU,
+    E.ToAddInputBf16 the atanh, to_add_input_conv_transp and add_input."""
+    g = upscaler_input.graph
+    for index in range(upscale_times):
+        scale, n = 2 ** (index + 1), "upscaling/" + str(index) + "/block"
+        near = resize_images(upscaler_input, scale // 2, "nearest", name=n + "/nearest")
+        bil = resize_images(upscaler_input, scale // 2, "bilinear", name=n + "/resize_bilinear")
+        up = concatenate([near, bil], name=n + "/upscaled_concat")
+        gate = E.UpGateConvBf16(n + "/attention", 6, model.channels, kernel_size)
+        model = KTensor(g, g.add("gate_conv", gate, [up.nid, model.nid]), model.channels)
+        convt = E.UpConvTBf16(n + "/conv_transp", model.channels, 128, kernel_size, L.ACT_LRELU, 0.2)
+        model = KTensor(g, g.add("convt", convt, [model.nid]), 128)
+        to_add = E.ToAddInputBf16(n + "/to_add_input_conv_transp", 3, 128, scale, 0.2)
+        model = KTensor(g, g.add("add_input", to_add, [upscaler_input.nid, model.nid]), 128)
+        # these layers exist in Keras (their names are taken); the nodes above compute them
+        g.names.update((n + "/attention_multiply", n + "/to_add_input_atanh", n + "/add_input"))
+    return KTensor(g, g.add("conv", E.FinalConv9x9C128Bf16("final/conv", 128, 3, 9), [model.nid]), 3)
 
 
 def make_upscaler_attention(output_image_shape, kernel_size=5, filters=64, upscale_factor=4, res_block_num=16, norm="batch", seed=7,
-                            trunk_dtype="fp32"):
+                            trunk_dtype="fp32", tail_dtype="fp32"):
     """make_upscaler_attention (model.py:299-328) -- the default generator of train_gan3.py (:55 'resnet-att', default -d 4) -- written
     block by block as the reference writes it.  Up-sampling block i resizes the input by 2**i (nearest and bilinear) for its attention
     and adds Conv2DTranspose(kernel 2**(i+1)+1, strides 2**(i+1)) of atanh(0.99999 * input) (E.ConvTDilated for strides 4).
@@ -620,17 +658,24 @@ def make_upscaler_attention(output_image_shape, kernel_size=5, filters=64, upsca
     batch_norm + add are stored bf16 NHWC, in training and in learning phase 0, on E.InitialConv9x9Bf16, E.GateConvBf16, E.Conv3x3Bf16 /
     E.Conv5x5Bf16 and E.NormActBf16 as nodes of the same graph; master weights, gradients, statistics, moving averages, BN and PReLU
     parameters stay fp32, layer names and parameter layouts are those of the fp32 model.  The up-sampling blocks and final/conv stay on
-    the fp32 layers.  ATTENTION_BF16_SERVED lists the shapes; others raise NotImplementedError."""
+    the fp32 layers.  ATTENTION_BF16_SERVED lists the shapes; others raise NotImplementedError.
+
+    tail_dtype='bf16' (needs trunk_dtype='bf16'): every activation from after_res/add to final/conv's input is stored bf16 NHWC as well, on
+    E.UpGateConvBf16, E.UpConvTBf16, E.ToAddInputBf16 and E.FinalConv9x9C128Bf16 (_attention_tail_bf16); the conversion behind
+    after_res/add disappears, the resize / concatenate nodes of the gates' input stay fp32 data nodes, frames go in and come out fp32 NCHW."""
     if trunk_dtype not in ("fp32", "bf16", "bf16+tail"):
         raise ValueError(trunk_dtype)
-    if trunk_dtype == "bf16+tail" or (trunk_dtype == "bf16" and (filters != 64 or output_image_shape[2] != 3 or norm != "batch"
-                                                               or kernel_size not in (3, 5) or upscale_factor not in (2, 4))):
+    if tail_dtype not in ("fp32", "bf16"):
+        raise ValueError(tail_dtype)
+    if trunk_dtype == "bf16+tail" or (tail_dtype == "bf16" and trunk_dtype != "bf16") or \
+            (trunk_dtype == "bf16" and (filters != 64 or output_image_shape[2] != 3 or norm != "batch" or kernel_size not in (3, 5)
+                                        or upscale_factor not in (2, 4))):
         raise NotImplementedError(ATTENTION_BF16_SERVED)
     input_image_shape = (output_image_shape[0] // upscale_factor, output_image_shape[1] // upscale_factor, output_image_shape[2])
     upscale_times = int(math.log(upscale_factor, 2))
     upscaler_input = Input(shape=input_image_shape, name="initial/input")
     if trunk_dtype == "bf16":
-        model = _attention_trunk_bf16(upscaler_input, kernel_size, res_block_num)
+        model = _attention_trunk_bf16(upscaler_input, kernel_size, res_block_num, to_f32=tail_dtype != "bf16")
     else:
         model = conv2d(upscaler_input, filters, 9, 1, "same", name="initial/conv")
         model = prelu(model, name="initial/prelu")
@@ -640,12 +685,15 @@ def make_upscaler_attention(output_image_shape, kernel_size=5, filters=64, upsca
         model = conv2d(model, filters, kernel_size, 1, "same", name="after_res/conv")
         model = batch_norm(model, name="after_res/batch_norm", norm=norm)
         model = add([upsc_model, model], name="after_res/add")
-    for index in range(upscale_times):
-        scale = 2 ** (index + 1)
-        model = upsampling_block_attention(model, upscaler_input, scale, kernel_size, 128, name="upscaling/" + str(index) + "/block")
-    model = conv2d(model, 3, 9, 1, "same", activation="tanh", name="final/conv")
+    if tail_dtype == "bf16":
+        model = _attention_tail_bf16(model, upscaler_input, kernel_size, upscale_times)
+    else:
+        for index in range(upscale_times):
+            scale = 2 ** (index + 1)
+            model = upsampling_block_attention(model, upscaler_input, scale, kernel_size, 128, name="upscaling/" + str(index) + "/block")
+        model = conv2d(model, 3, 9, 1, "same", activation="tanh", name="final/conv")
     net = build_model(upscaler_input, model, name="upscaler_attention", seed=seed)
-    net.trunk_dtype = trunk_dtype
+    net.trunk_dtype, net.tail_dtype = trunk_dtype, tail_dtype
     # what the bf16 inference engine recognises the topology by (not the name string), and its entry point
     net.attention_generator = {"kernel_size": kernel_size, "filters": filters, "upscale_factor": upscale_factor, "res_block_num": res_block_num,
                                "norm": norm, "channels": output_image_shape[2]}

@@ -161,6 +161,15 @@ SIGNATURES = {
     "vcg_conv_in_gate_bf16_fwd": (c_int, [_D, _P, _P, _P, _P, _P, _P]),
     "vcg_conv_in_gate_bf16_bwd": (c_int, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vcg_input_convt_add_bf16": (c_int, [_D, _P, _P, _P, _P, _P]),
+    # bf16 tail training of make_upscaler_attention
+    "vcg_conv_in_gate_up_bf16_bwd": (c_int, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vcg_conv_in_gate_up_bf16_wgrad_ws_bytes": (c_size_t, [_D]),
+    "vcg_conv_in_gate_up_bf16_wgrad": (c_int, [_D, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "vcg_conv9x9_c128to3_bf16_wgrad_ws_bytes": (c_size_t, [_D]),
+    "vcg_conv9x9_c128to3_bf16_wgrad": (c_int, [_D, _P, _P, _P, _P, c_size_t, _P]),
+    "vcg_input_convt_add_bf16_to": (c_int, [_D, _P, _P, _P, _P, _P, _P]),
+    "vcg_input_convt_add_bf16_bwd_ws_bytes": (c_size_t, [_D]),
+    "vcg_input_convt_add_bf16_bwd": (c_int, [_D, _P, _P, _P, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
     # generic bf16 NHWC convolution
     "vcg_conv_frag_bf16_bytes": (c_size_t, [c_int, c_int, c_int]),
     "vcg_pack_conv_frag_bf16": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
