@@ -1,6 +1,8 @@
 """GPU parity of every C-ABI kernel family against the CPU oracle (oracle/keras_ops.py) on the same
 seeded inputs.  Tolerance: 1e-3 max-norm relative (north_star: "within 1e-3 rel fp32"); the fp32 MFMA
-path is an exact fp32 FMA chain so observed errors are ~1e-6 (written to gpurun_out/parity_report.txt)."""
+path is an exact fp32 FMA chain so observed errors are ~1e-6 (written to the parity report of conftest.report).
+That "~1e-6" is enforced, output by output, in tests/test_fp32_chain_precision_gpu.py; the bound here cannot tell fp32 from tf32
+arithmetic."""
 import ctypes
 
 import numpy as np
