@@ -615,6 +615,84 @@ int vcg_lrelu_bwd_bf16(const void* dy, const void* y_act, float slope, void* dx,
 int vcg_bf16_to_f32(const void* x, float* y, size_t count, hipStream_t stream);
 int vcg_f32_to_bf16(const float* x, void* y, size_t count, hipStream_t stream);
 
+/* ---- bf16 inference of make_upscaler_incep_resnet (upscaling/upscaler/model.py:443-497; train_gan3.py -gm inc-resnet) ------------------
+ * An inception block (model.py:386-412 3-path, :416-439 2-path) is  m -> paths of [BatchNormalization -> PReLU -> Conv2D] mini-blocks
+ * (model.py:372-382) -> Concatenate -> Conv2D 1x1 -> Add(m).  In learning phase 0 a BatchNormalization is a per-channel scale / shift: a
+ * layer whose output has one consumer applies that consumer's BN + PReLU in its own epilogue and stores the ACTIVATED tensor; only the
+ * block input m (64 channels, read by every path and the Add) is activated on load.  One launch each:
+ *     head   every path's first mini-block, a 1x1 on m            vcg_incep_head_bf16_fwd
+ *     middle 3x3 / 5x5 / 1xk / kx1 + the next mini-block's BN/PReLU vcg_conv2d_nhwc_bf16_fwd_epilogue
+ *     join   Concatenate + Conv2D 1x1 + Add                        vcg_incep_join_bf16_fwd
+ * Tensors are bf16 NHWC, MFMA operands bf16, accumulation and epilogue arithmetic fp32.
+ * Channel padding: the paths have 19, 25, 32, 48 or 64 channels.  A stored tensor, a packed kernel (both of its channel axes) and an
+ * epilogue vector hold vcg_incep_padded_channels(c) = the next multiple of 32 channels.  vcg_pack_incep_frag_bf16 and vcg_incep_fold write
+ * zeros into the padding, so that every kernel below stores +0 in the padded channels of every pixel and no consumer multiplies a zero
+ * weight with uninitialised memory.  None of the entries needs a workspace or scratch memory; all are hipGraph-capturable. */
+int32_t vcg_incep_padded_channels(int32_t c);
+/* bytes of vcg_pack_incep_frag_bf16's output for `taps` x cin x cout: taps * padded(cin) * padded(cout) * 2; 0 for a non-positive argument */
+size_t vcg_incep_frag_bf16_bytes(int32_t taps, int32_t cin, int32_t cout);
+/* rows [k0, k0 + kcount) of the input-channel axis of a Keras (kh,kw,cin_total,cout) fp32 kernel (taps = kh*kw) as the generic kernels'
+ * MFMA fragments (vcg_pack_conv_frag_bf16 mode 0) of a padded(kcount) -> padded(cout) layer, rounded to bf16, zeros in the padding;
+ * out = vcg_incep_frag_bf16_bytes(taps, kcount, cout).  A whole layer: k0 = 0, kcount = cin_total.  One source of the join (model.py:409-410,
+ * 436-437): its rows of the (1,1,128 | 64,64) kernel.  VCG_E_NULL: w or out NULL; VCG_E_SHAPE: a non-positive size, k0 < 0 or
+ * k0 + kcount > cin_total; VCG_E_UNSUPPORTED: taps > 25, cout > 64 or kcount > 64. */
+int vcg_pack_incep_frag_bf16(const float* w, int32_t taps, int32_t cin_total, int32_t cout, int32_t k0, int32_t kcount, void* out,
+                             hipStream_t stream);
+/* the epilogue vectors of a layer with c (<= 64) output channels, padded(c) floats each, zeros in the padding: the layer's bias folded with
+ * the inference-mode BatchNormalization of the mini-block that consumes it (model.py:374-375; vcg_bn_fold's arithmetic),
+ *     scale = gamma * rsqrt(moving_var + eps), shift = (bias - moving_mean) * scale + beta,      alpha_out = alpha (model.py:377)
+ * bias / gamma / beta may be NULL (0 / 1 / 0); moving_mean == moving_var == NULL: no normalisation, scale = 1, shift = bias (path a/1, whose
+ * consumer is the concatenation); alpha and alpha_out are both given or both NULL.  With bias NULL these are the vectors of a
+ * BatchNormalization + PReLU applied to a stored tensor: the head's pre-activation of m.  VCG_E_NULL: scale or shift NULL, one of
+ * moving_mean / moving_var or of alpha / alpha_out without the other; VCG_E_SHAPE: c <= 0; VCG_E_UNSUPPORTED: c > 64. */
+int vcg_incep_fold(const float* bias, const float* moving_mean, const float* moving_var, const float* gamma, const float* beta, const float* alpha,
+                   int32_t c, float eps, float* scale, float* shift, float* alpha_out, hipStream_t stream);
+/* Block head (model.py:392-393,395 and :422-423: a/1, b/1 [, c/1], each BatchNormalization -> PReLU -> Conv2D 1x1 on the block input;
+ * with b/2's and c/2's BatchNormalization -> PReLU, model.py:394,396,424, in the epilogue).  m bf16 NHWC [n][h][w][64] is read once; per path p
+ *     u = prelu(in_scale * m + in_shift; in_alpha)       fp32, rounded once to bf16: the MFMA operand
+ *     y = act(out_scale * (W u) + out_shift)             bf16 NHWC [n][h][w][32]; act = PReLU(out_alpha), or none where out_alpha is NULL
+ * in_*: 64 floats (vcg_incep_fold without bias); wfrag: vcg_pack_incep_frag_bf16(w (1,1,64,cout), 1, 64, cout, 0, 64); out_*: 32 floats
+ * (vcg_incep_fold of the path's bias and its consumer).  cout[p] <= 32 channels per path (32 / 32 / 32 and 32 / 19 in the reference).
+ * VCG_E_NULL: d, m, paths or a path's pointer other than out_alpha NULL; VCG_E_SHAPE: n, h, w or a cout <= 0, n*h*w*128 bytes beyond 4 GiB;
+ * VCG_E_UNSUPPORTED: cin != 64, npaths outside 1..3, a cout > 32. */
+typedef struct vcg_incep_head_desc {
+    int32_t n, h, w, cin, npaths;
+    int32_t cout[3];
+} vcg_incep_head_desc;
+typedef struct vcg_incep_head_path {
+    const float* in_scale;
+    const float* in_shift;
+    const float* in_alpha;
+    const void* wfrag;
+    const float* out_scale;
+    const float* out_shift;
+    const float* out_alpha;
+    void* y;
+} vcg_incep_head_path;
+int vcg_incep_head_bf16_fwd(const vcg_incep_head_desc* d, const void* m, const vcg_incep_head_path* paths, hipStream_t stream);
+/* The layers between head and join (model.py:394,396-397 3x3 / 5x5 on 32 -> 32, 32 -> 48, 48 -> 64; :424-425 1xk / kx1, k = 3, 5, 7, on
+ * 19 -> 25, 25 -> 32): Conv2D stride 1 'same' with the whole per-channel epilogue y = act(scale[c] * acc + shift[c]), act = none or
+ * PReLU(prelu_alpha[c]), on the generic kernels.  d names the layer's own cin / cout (both <= 64; a 1xk / kx1 layer: both <= 32) and pads =
+ * (kh / 2, kw / 2); x [n][h][w][padded(cin)] and y [n][h][w][padded(cout)] bf16 NHWC; wfrag = vcg_pack_incep_frag_bf16(w, kh*kw, cin, cout, 0,
+ * cin); ep->scale / shift / prelu_alpha: padded(cout) floats from vcg_incep_fold.  VCG_E_NULL: d, ep, x, wfrag, y, ep->scale, ep->shift or
+ * (with VCG_ACT_PRELU) ep->prelu_alpha NULL; VCG_E_SHAPE: non-positive sizes, oh / ow other than h / w, other pads, a tensor beyond 4 GiB;
+ * VCG_E_UNSUPPORTED: stride != 1, another kernel size or channel count, another activation, ep->residual or ep->stats_mode set. */
+int vcg_conv2d_nhwc_bf16_fwd_epilogue(const vcg_conv_desc* d, const void* x, const void* wfrag, void* y, const vcg_epilogue_bf16* ep,
+                                      hipStream_t stream);
+/* Block join (model.py:409-411, 436-438: Concatenate -> Conv2D 1x1 (64) -> Add with the block input):
+ *     y = m + bias + sum over the nsrc sources of W_s z_s           fp32, rounded once to bf16
+ * z[s] bf16 NHWC [n][h][w][padded(cin[s])], wfrag[s] = vcg_pack_incep_frag_bf16(w (1,1,sum cin,64), 1, sum cin, 64, k0 = cin[0] + .. +
+ * cin[s-1], cin[s]): the concatenation is never stored (cin = 32, 32, 64 and 32, 32 in the reference).  z and wfrag are HOST arrays of
+ * nsrc device pointers, read at call time.  bias fp32 [64]; m and y bf16 NHWC [n][h][w][64]; y may be m, not a source.  VCG_E_NULL: any
+ * pointer NULL; VCG_E_SHAPE: n, h, w or a cin <= 0, n*h*w*128 bytes beyond 4 GiB; VCG_E_UNSUPPORTED: cout != 64, nsrc outside 1..3, a
+ * cin > 64, y == z[s]. */
+typedef struct vcg_incep_join_desc {
+    int32_t n, h, w, cout, nsrc;
+    int32_t cin[3];
+} vcg_incep_join_desc;
+int vcg_incep_join_bf16_fwd(const vcg_incep_join_desc* d, const void* const* z, const void* const* wfrag, const float* bias, const void* m,
+                            void* y, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,11 @@ batch.  Prints one JSON line per run, shaped like ``bench.py --config c5``'s.
            arms timed by HIP events (--ab-reps repetitions each, median and min-max); --full times one launch of each kind the pass makes on
            the engine's own buffers, with FLOP/s and the bytes each must move per second
 
+  --generator inc-resnet  make_upscaler_incep_resnet (model.py:443-497, train_gan3.py's -gm inc-resnet) at its defaults (5 3-path k3, 10 2-path
+           k7, 5 2-path k3 blocks, x4; --incep-blocks A B C changes the counts) through its to_inference_bf16(); --kernel-size and
+           --res-blocks do not apply.  --fp32 also alternates the bf16 replay and fp32 G.forward as two arms timed by HIP events; --full times
+           one block of each kind (its 5 / 4 launches) and the launches around them on the engine's own buffers
+
   --fp32   also times the fp32 product path (G.forward, i.e. what G.predict runs per batch) on the same weights and frames; it may run a
            smaller batch per call (--fp32-batch), stated in its line
   --full   per-layer HIP-event times of the bf16 pass (the calls the engine makes, on its buffers), with algorithmic FLOP, TFLOP/s and the
@@ -29,7 +34,8 @@ batch.  Prints one JSON line per run, shaped like ``bench.py --config c5``'s.
 
 Usage: python scripts/bench_infer_bf16.py [--lr-size 128] [--lr-width W] [--batch 32] [--kernel-size 5] [--upscale 4] [--res-blocks 16]
                                           [--steps 10] [--warmup 3] [--fp32] [--full] [--u8] [--band-rows R] [--band-sweep R [R ...]]
-                                          [--generator orig|attention|cyclegan] [--n-downsample 2] [--norm instance]"""
+                                          [--generator orig|attention|cyclegan|inc-resnet] [--n-downsample 2] [--norm instance]
+                                          [--incep-blocks 5 10 5]"""
 import argparse
 import ctypes
 import json
@@ -95,6 +101,24 @@ def flop_frame_cyclegan(h, w, k, f, res, nd):
     return t + flop_conv(1, hh, ww, 64, 3, 9)
 
 
+def flop_frame_incep(h, w, f, groups, kc):
+    """make_upscaler_incep_resnet with 64 filters: groups = [(block type, count, kernel)]; prefinal and the tail on kernel kc"""
+    px = lambda cin, cout, taps: 2.0 * h * w * cin * cout * taps
+    t = flop_conv(1, h, w, 3, 64, 9)
+    for btype, num, k in groups:
+        if btype == "3path":
+            blk = 3 * px(64, 32, 1) + px(32, 32, k * k) + px(32, 48, k * k) + px(48, 64, k * k) + px(128, 64, 1)
+        else:
+            blk = px(64, 32, 1) + px(64, 19, 1) + px(19, 25, k) + px(25, 32, k) + px(64, 64, 1)
+        t += num * blk
+    t += flop_conv(1, h, w, 64, 64, kc)
+    hh, ww, cin = h, w, 64
+    while f > 1:
+        t += flop_convt(1, hh, ww, cin, 256, kc)
+        hh, ww, cin, f = 2 * hh, 2 * ww, 256, f // 2
+    return t + flop_conv(1, hh, ww, 256, 3, 9)
+
+
 def time_events(fn, reps, warm=2):
     import torch
     for _ in range(warm):
@@ -122,7 +146,8 @@ def main():
     ap.add_argument("--fp32-batch", type=int, default=4)
     ap.add_argument("--full", action="store_true")
     ap.add_argument("--ab-reps", type=int, default=5)
-    ap.add_argument("--generator", choices=("orig", "attention", "cyclegan"), default="orig")
+    ap.add_argument("--generator", choices=("orig", "attention", "cyclegan", "inc-resnet"), default="orig")
+    ap.add_argument("--incep-blocks", type=int, nargs=3, default=(5, 10, 5), metavar=("A", "B", "C"))
     ap.add_argument("--n-downsample", type=int, default=2)
     ap.add_argument("--norm", choices=("instance", "batch"), default=None)
     ap.add_argument("--u8", action="store_true")
@@ -139,12 +164,18 @@ def main():
     h, B, k, f, res = args.lr_size, args.batch, args.kernel_size, args.upscale, args.res_blocks
     w = args.lr_width or h
     frame = "%dx%d->%dx%d" % (h, w, f * h, f * w)
-    att, cyc = args.generator == "attention", args.generator == "cyclegan"
+    att, cyc, inc = args.generator == "attention", args.generator == "cyclegan", args.generator == "inc-resnet"
     make = PM.make_upscaler_attention if att else PM.make_generator_cyclegan if cyc else PM.make_upscaler_orig
     kw = {} if args.norm is None and not cyc else {"norm": args.norm or "instance"}
     if cyc:
         kw["n_downsample"] = args.n_downsample
-    G = make((f * h, f * w, 3), kernel_size=k, upscale_factor=f, res_block_num=res, seed=7, **kw)
+    if inc:
+        make, (na, nb_, nc) = PM.make_upscaler_incep_resnet, args.incep_blocks
+        G = make((f * h, f * w, 3), upscale_factor=f, a_block_num=na, b_block_num=nb_, c_block_num=nc, seed=7)
+        groups = [("3path", na, 3), ("2path", nb_, 7), ("2path", nc, 3)]
+        k = 3                                  # c_block_kernel: prefinal/conv2d and the tail
+    else:
+        G = make((f * h, f * w, 3), kernel_size=k, upscale_factor=f, res_block_num=res, seed=7, **kw)
     inf = G.to_inference_bf16()
     rt = inf.rt
     g1 = torch.Generator().manual_seed(1234)
@@ -159,8 +190,10 @@ def main():
         inf.replay(x, br)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    fl = flop_frame_attention(h, w, k, f, res) if att else flop_frame_cyclegan(h, w, k, f, res, args.n_downsample) if cyc else flop_frame(h, w, k, f, res)
+    fl = flop_frame_incep(h, w, f, groups, k) if inc else flop_frame_attention(h, w, k, f, res) if att else flop_frame_cyclegan(h, w, k, f, res, args.n_downsample) if cyc else flop_frame(h, w, k, f, res)
     wl = "%s((%d,%d,3),k=%d,x%d,res=%d%s)" % (make.__name__, f * h, f * w, k, f, res, "".join(",%s=%s" % kv for kv in sorted(kw.items())))
+    if inc:
+        wl = "%s((%d,%d,3),x%d,blocks=%d/%d/%d)" % ((make.__name__, f * h, f * w, f) + tuple(args.incep_blocks))
     bf = {"metric": "upscaled frames/s (inference, generator only, bf16) at %s" % frame, "value": round(B * args.steps / dt, 2),
           "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
           "higher_is_better": True, "dtype": "bf16", "data": "synthetic",
@@ -198,11 +231,11 @@ def main():
                           "config": {"workload": "G.forward(x, training=False) -- what G.predict runs per batch -- same weights and frames, "
                                                  "batch %d per call (eager launches)" % b32, "global_batch": b32, "frame": frame}}), flush=True)
 
-    if args.fp32 and cyc:
+    if args.fp32 and (cyc or inc):
         ab_fp32(args, G, inf, x, B, frame)
 
     if args.full:
-        (full_attention if att else full_cyclegan if cyc else full)(args, inf, x, h, w, k, f, res, B)
+        (full_incep if inc else full_attention if att else full_cyclegan if cyc else full)(args, inf, x, h, w, k, f, res, B)
 
 
 def band_sweep(args, inf, x, h, w, k, f, B):
@@ -509,6 +542,72 @@ def full_cyclegan(args, inf, x, h, w, k, f, res, B):
         flop_conv(ch, hh, ww, 64, 3, 9), src.numel() * 2 + y8.numel(), 1)
     for r in rows:
         print(json.dumps(dict(r, kind="layer")), flush=True)
+
+
+def full_incep(args, inf, x, h, w, k, f, res, B):
+    """the inc-resnet pass on the engine's own buffers, by HIP events: the stem, one block of each kind (all its launches: head, the layers
+    between, join), prefinal/conv2d, the up-sampling stages and final/conv on the engine's chunk of frames; algorithmic FLOP and TFLOP/s, and for
+    the blocks the bytes their launches must move (every tensor read + written once, bf16) per second"""
+    import torch
+    from upscaler import _lib as L
+    rt, lib, st = inf.rt, inf.rt.lib, inf.rt.stream
+    Bf = inf._buffers(B, h, w)
+    inf.forward(x)                                    # every buffer holds a pass's data
+    torch.cuda.synchronize()
+    rows = []
+
+    def row(name, ms, flop, nbytes=0, extra=None):
+        d = {"layer": name, "ms": round(ms, 4), "gflop": round(flop / 1e9, 2), "tflops": round(flop / ms / 1e9, 1),
+             "peak_share": round(flop / (ms * 1e-3) / PEAK_BF16, 4)}
+        if nbytes:
+            d.update({"must_move_gb": round(nbytes / 1e9, 3), "tb_per_s": round(nbytes / (ms * 1e-3) / 1e12, 3)})
+        d.update(extra or {})
+        rows.append(d)
+
+    w0, b0, _ = inf.first
+    row("initial/conv/9x9 3->64", time_events(lambda: inf._stem(x, w0, b0, None, Bf["skip"]), args.ab_reps), flop_conv(B, h, w, 3, 64, 9))
+    kinds = {}
+    for blk in inf.blocks:
+        key = (len(blk["heads"]), blk["mids"][0]["kh"], blk["mids"][0]["kw"])
+        kinds.setdefault(key, []).append(blk)
+    px = B * h * w
+    for (nh, kh, kw), blks in kinds.items():
+        blk = blks[0]
+        fl = sum(2.0 * px * 64 * hp["cout"] for hp in blk["heads"]) + sum(2.0 * px * m["cin"] * m["cout"] * m["kh"] * m["kw"] for m in blk["mids"]) \
+            + 2.0 * px * sum(c for _, c, _ in blk["srcs"]) * 64
+        # stored channels moved: head reads 64, writes 32 per path; each middle layer reads and writes its padded tensors; join reads its
+        # sources and m, writes 64
+        pad = lambda c: (c + 31) // 32 * 32
+        ch_moved = 64 + 32 * nh + sum(pad(m["cin"]) + pad(m["cout"]) for m in blk["mids"]) + sum(pad(c) for _, c, _ in blk["srcs"]) + 64 + 64
+        name = "%s block, kernel %dx%d (x%d per pass): %d launches" % ("3-path" if nh == 3 else "2-path", kh, kw, len(blks), 2 + len(blk["mids"]))
+        row(name, time_events(lambda: inf._run_block(blk, Bf["skip"], Bf["a"], Bf, B, h, w), args.ab_reps), fl, px * ch_moved * 2)
+    wp, sp, hp_ = inf.prefinal
+    row("prefinal/conv2d %dx%d 64->64 + BN + Add" % (k, k),
+        time_events(lambda: inf._conv(Bf["a"], wp, Bf["c"], sp, hp_, L.ACT_NONE, None, Bf["skip"], B, h, w), args.ab_reps), flop_conv(B, h, w, 64, 64, k))
+    us = Bf["us"]
+    ch = us[0].shape[0]
+    hh, ww, cin = h, w, 64
+    for i in range(len(inf.ups)):
+        src = Bf["c"][:ch] if i == 0 else us[i - 1]
+        row("upscaling/%d ConvT %dx%d s2 %d->256 at %dx%d, %d frames per launch" % (i, k, k, cin, 2 * hh, 2 * ww, ch),
+            time_events(lambda: upsample_one(inf, i, src, us[i], ch, hh, ww), args.ab_reps), flop_convt(ch, hh, ww, cin, 256, k))
+        hh, ww, cin = 2 * hh, 2 * ww, 256
+    row("final/conv 9x9 256->3 at %dx%d, %d frames per launch" % (hh, ww, ch),
+        time_events(lambda: inf._to3(us[-1], Bf["y"][:ch]), args.ab_reps), flop_conv(ch, hh, ww, 256, 3, 9))
+    for r in rows:
+        print(json.dumps(dict(r, kind="layer")), flush=True)
+    print(json.dumps({"kind": "launches", "entry_point_calls_per_pass_one_chunk": inf.launches(), "tail_frames_per_launch": ch,
+                      "blocks": len(inf.blocks)}), flush=True)
+
+
+def upsample_one(inf, i, src, dst, c, hh, ww):
+    """stage i of the engine's up-sampling alone (Bf16Generator._upsample on a one-stage view)"""
+    ups, layers = inf.ups, inf.up_layers
+    inf.ups, inf.up_layers = ups[i:i + 1], layers[i:i + 1]
+    try:
+        inf._upsample(src, [dst], c, hh, ww)
+    finally:
+        inf.ups, inf.up_layers = ups, layers
 
 
 def ab(rows, name, new, gen, flop, reps):

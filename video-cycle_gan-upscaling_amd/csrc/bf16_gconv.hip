@@ -13,7 +13,7 @@
 // address path (one 16-byte load per MFMA and wave), i.e. it cannot reach the MFMA roof the LDS-tiled trunk kernel aims
 // at -- but it serves every shape with one code path at several times the fp32 kernels' rate, and the data gradient of a
 // strided convolution is the same kernel run once per output phase with that phase's tap list.
-#include "vcg_common.hpp"
+#include "bf16_tiles.hpp"          // ld_frag
 
 namespace {
 
@@ -44,10 +44,6 @@ struct GcParams {
     float* stats;           // LDS-tiled kernel only: per-tile sums / sums of squares of the stored output, [n][tiles per image][2][mch]
     GcTap taps[GC_MAXTAPS];
 };
-
-__device__ __forceinline__ bf16x8 ld_frag(vcg_rsrc r, unsigned off) {
-    return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
-}
 
 // workgroup = 4 waves; wave = 64 output channels (2 MFMA row blocks) x NT tiles of 32 consecutive logical pixels
 // EPI: the vcg_epilogue_bf16 terms (scale, per-channel PReLU slope, residual) -- a separate instantiation, so the layers that do not
@@ -829,6 +825,38 @@ int vcg_gconv5x5_c64_bf16_fwd(const vcg_conv_desc* d, const void* x, const void*
     p.prelu = p.act == VCG_ACT_PRELU ? (const float*)ep->prelu_alpha : nullptr;
     if (p.act == VCG_ACT_PRELU) p.act = VCG_ACT_LRELU;          // the epilogue's negative-side slope is then prelu[c]
     p.res = ep ? ep->residual : nullptr;
+    return launch_gconv(p, stream);
+}
+
+// the layers between an inception block's head and join (model.py:392-396 3x3 / 5x5 on 32 -> 32, 32 -> 48, 48 -> 64; :423-424 1xk / kx1 on
+// 19 -> 25, 25 -> 32) on this file's kernels with the whole per-channel epilogue, y = prelu(acc * scale + shift): the layer's bias and its
+// single consumer's inference-mode BatchNormalization + PReLU (model.py:374-377), folded by vcg_incep_fold.  d names the layer's own channel
+// counts; tensors, fragments and epilogue vectors are padded to multiples of 32 (vcg_incep_padded_channels), zeros in the padding.
+int vcg_conv2d_nhwc_bf16_fwd_epilogue(const vcg_conv_desc* d, const void* x, const void* wfrag, void* y, const vcg_epilogue_bf16* ep,
+                                      hipStream_t stream) {
+    if (d == nullptr || ep == nullptr) return VCG_E_NULL;
+    VCG_CHECK_PTR(x); VCG_CHECK_PTR(wfrag); VCG_CHECK_PTR(y); VCG_CHECK_PTR(ep->scale); VCG_CHECK_PTR(ep->shift);
+    if (d->n <= 0 || d->cin <= 0 || d->h <= 0 || d->w <= 0 || d->cout <= 0 || d->oh != d->h || d->ow != d->w) return VCG_E_SHAPE;
+    const bool square = d->kh == d->kw && (d->kh == 3 || d->kh == 5);
+    const int kl = d->kh == 1 ? d->kw : d->kh;
+    const bool line = (d->kh == 1 || d->kw == 1) && d->kh != d->kw && (kl == 3 || kl == 5 || kl == 7);
+    if (d->stride != 1 || !(square || line) || d->cin > 64 || d->cout > 64 || (line && (d->cin > 32 || d->cout > 32))) return VCG_E_UNSUPPORTED;
+    if (d->pad_top != d->kh / 2 || d->pad_left != d->kw / 2) return VCG_E_SHAPE;
+    if (ep->act != VCG_ACT_NONE && ep->act != VCG_ACT_PRELU) return VCG_E_UNSUPPORTED;
+    if (ep->act == VCG_ACT_PRELU) VCG_CHECK_PTR(ep->prelu_alpha);
+    if (ep->residual != nullptr || ep->stats_mode != VCG_STATS_NONE) return VCG_E_UNSUPPORTED;
+    vcg_conv_desc dp = *d;
+    dp.cin = (d->cin + 31) & ~31;
+    dp.cout = (d->cout + 31) & ~31;
+    int rc = check_gdesc(&dp);
+    if (rc) return rc;
+    GcParams p{};
+    p.x = x; p.wf = wfrag; p.y = y;
+    fwd_params(&dp, p);
+    p.bias = (const float*)ep->shift;
+    p.scale = (const float*)ep->scale;
+    p.prelu = ep->act == VCG_ACT_PRELU ? (const float*)ep->prelu_alpha : nullptr;
+    p.act = ep->act == VCG_ACT_PRELU ? VCG_ACT_LRELU : VCG_ACT_NONE;         // the epilogue's negative-side slope is then prelu[c]
     return launch_gconv(p, stream);
 }
 

@@ -23,6 +23,26 @@ __device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
+// one 16-byte operand fragment (8 bf16) through a range-checked descriptor: VCG_OOB reads as zeros (the generic kernels of bf16_gconv.hip
+// and the inception block's 1x1 kernels of bf16_incep.hip)
+__device__ __forceinline__ bf16x8 ld_frag(vcg_rsrc r, unsigned off) {
+    return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
+}
+
+// A 32x32 MFMA tile leaves lane (column r, half hh) with rows 8g + 4hh + {0..3} in register group g; v_permlane32_swap between the groups
+// (2q, 2q+1) of the two half-waves turns that into 8 consecutive rows 16q + 8hh + {0..7} in v: with rows = output channels, one 16-byte
+// NHWC store per q.  Every lane of the wave must call it.  (The epilogues of bf16_gconv.hip, bf16_conv3x3_3ch.hip and bf16_convt3x3.hip
+// spell the same four swaps out in place: routed through this function the generic kernels' schedule changed, scripts/device_isa.py.)
+__device__ __forceinline__ void acc_channels8(const f32x16& acc, int q, float (&v)[8]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float lo = acc[8 * q + j], hi = acc[8 * q + 4 + j];
+        swap32(lo, hi);
+        v[j] = lo;
+        v[4 + j] = hi;
+    }
+}
+
 // The 6 + 2-wave skeleton of conv3x3_c64_bf16_kernel (bf16_conv3x3_3ch.hip, where it is described), shared by conv_c3to64_bf16_kernel and
 // convt3x3_c64_bf16_kernel: 12x32-pixel tiles, 128-byte pixel rows, the 3x3 weights of one 64-channel output block resident in LDS
 constexpr int NCW = 6, NLW = 2;             // compute / loader waves

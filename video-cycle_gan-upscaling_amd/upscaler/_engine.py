@@ -755,6 +755,27 @@ def pack_conv_frag_bf16(rt, w, taps, mdim, kdim, mode, out=None):
     return out
 
 
+def pack_incep_frag_bf16(rt, w, taps, cin_total, cout, k0=0, kcount=None, out=None):
+    """rows [k0, k0 + kcount) of the input-channel axis of a Keras (kh,kw,cin_total,cout) kernel as the generic kernels' fragments, both
+    channel axes padded with zeros to multiples of 32 (include/vcg.h: vcg_pack_incep_frag_bf16)"""
+    kcount = cin_total if kcount is None else kcount
+    out = _bytes(rt, rt.lib.vcg_incep_frag_bf16_bytes(taps, kcount, cout)) if out is None else out
+    L.check(rt.lib.vcg_pack_incep_frag_bf16(w.data_ptr(), taps, cin_total, cout, k0, kcount, out.data_ptr(), rt.stream), "vcg_pack_incep_frag_bf16")
+    return out
+
+
+def incep_fold(rt, ps, c, bias=None, norm=None, prelu=None):
+    """(scale, shift, alpha) of c channels padded with zeros to a multiple of 32: the bias named `bias`, folded with the inference-mode
+    BatchNormalization named `norm`, and the PReLU slopes named `prelu` (each optional; include/vcg.h: vcg_incep_fold)"""
+    cp = rt.lib.vcg_incep_padded_channels(c)
+    scale, shift, alpha = rt.empty(cp), rt.empty(cp), rt.empty(cp) if prelu else None
+    p = lambda name: ps[name].data_ptr() if name else None
+    L.check(rt.lib.vcg_incep_fold(p(bias and bias + "/bias"), p(norm and norm + "/moving_mean"), p(norm and norm + "/moving_variance"),
+                                  p(norm and norm + "/gamma"), p(norm and norm + "/beta"), p(prelu and prelu + "/alpha"), c, BN_EPS,
+                                  scale.data_ptr(), shift.data_ptr(), _ptr(alpha), rt.stream), "vcg_incep_fold")
+    return scale, shift, alpha
+
+
 def pack_conv_frag_bf16_pair(rt, w, taps, cin, cout, out=None):
     """modes 0 and 1 of a Keras (k,k,cin,cout) kernel in one launch -> (forward, data gradient)"""
     wf, wd = (_bf16(rt, taps, cout, cin), _bf16(rt, taps, cin, cout)) if out is None else out

@@ -238,4 +238,17 @@ def make_upscaler_incep_resnet(output_image_shape, filters=64, upscale_factor=4,
     for index in range(upscale_times):
         model = G.upsampling_block(model, c_block_kernel, 256, 2, name="upscaling/" + str(index) + "/block")
     model = G.conv2d(model, 3, 9, 1, "same", activation="tanh", name="final/conv")
-    return G.build_model(upscaler_input, model, name="upscaler_incep_resnet", seed=seed)
+    net = G.build_model(upscaler_input, model, name="upscaler_incep_resnet", seed=seed)
+    # what the bf16 inference engine recognises the topology by (not the name string), and its entry point
+    net.incep_resnet_generator = {"filters": filters, "upscale_factor": upscale_factor, "channels": output_image_shape[2],
+                                  "a_block_type": a_block_type, "a_block_num": a_block_num, "a_block_kernel": a_block_kernel,
+                                  "b_block_type": b_block_type, "b_block_num": b_block_num, "b_block_kernel": b_block_kernel,
+                                  "c_block_type": c_block_type, "c_block_num": c_block_num, "c_block_kernel": c_block_kernel}
+    net.to_inference_bf16 = lambda: _incep_resnet_bf16(net)
+    return net
+
+
+def _incep_resnet_bf16(net):
+    """inference engine on the bf16-storage kernels (BN folded into epilogues, one hipGraph per input shape): ``_infer.Bf16IncepResnetGenerator``"""
+    from ._infer import Bf16IncepResnetGenerator
+    return Bf16IncepResnetGenerator(net)

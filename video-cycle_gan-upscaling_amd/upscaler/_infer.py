@@ -200,6 +200,7 @@ class Bf16Generator:
         sp, hp = self._fold(m.c_pre, m.n_pre)
         self.prefinal = (self._pack(m.c_pre, 1), sp, hp)
         # one weight set per up-sampling stage: 64 -> 256, then 256 -> 256 (model.py:286-288)
+        self.up_layers = m.ups
         self.ups = [(self._pack(up, 0), up.ps[up.name + "/bias"], float(up.alpha), up.cin) for up in m.ups]
         self.up = self.ups[0][:3]
         self.final = (E.pack_final9x9_bf16(rt, m.c_fin.ps[m.c_fin.name + "/kernel"]), m.c_fin.ps[m.c_fin.name + "/bias"])
@@ -381,7 +382,7 @@ class Bf16Generator:
         """the up-sampling stages on c frames of hh x ww pixels (a whole image or a band: a band is a shorter image) into the buffers us;
         returns the last stage's output and its size"""
         rt, k, crop = self.rt, self.k, max(self.k - 2, 0) // 2           # TF-SAME crop of Conv2DTranspose(k, strides 2): k3 (0, 1), k5 (1, 2)
-        for (wt, bt, slope, cin), up, u in zip(self.ups, self.model.ups, us):
+        for (wt, bt, slope, cin), up, u in zip(self.ups, self.up_layers, us):
             dt = L.ConvDesc(c, cin, hh, ww, 256, 2 * hh, 2 * ww, k, k, 2, crop, crop)
             if self._generic(up, 0):
                 L.check(rt.lib.vcg_conv_transpose2d_nhwc_bf16_fwd(ctypes.byref(dt), src.data_ptr(), wt.data_ptr(), bt.data_ptr(), L.ACT_LRELU,
@@ -894,4 +895,191 @@ class Bf16CycleGanGenerator(Bf16Generator):
         y = self._bufs[key]
         for i in range(0, n, ch):
             self._pass(x[i:i + ch], y[i:i + ch], out_kind, taps)
+        return y
+
+
+class Bf16IncepResnetGenerator(Bf16Generator):
+    """The same engine for ``make_upscaler_incep_resnet`` models (upscaling/upscaler/model.py:443-497; train_gan3.py's ``-gm inc-resnet``),
+    filters 64 on RGB frames, upscale_factor a power of two >= 2, any number (0 included) of '3path' (kernel 3 or 5) and '2path' (kernel 3, 5
+    or 7) blocks, c_block_kernel 3 or 5:
+
+        initial/conv/9x9 3->64 + bias (no activation: the long skip)   vcg_conv9x9_from3_bf16_fwd
+        3-path block (model.py:386-412), 5 launches:
+            a/1, b/1, c/1: BN + PReLU of m on load, 1x1, + b/2's and c/2's BN + PReLU    vcg_incep_head_bf16_fwd  -> a1 (raw), b1, c1 (activated)
+            b/2 kxk 32->32 + bias; c/2 kxk 32->48 + c/3's BN + PReLU; c/3 kxk 48->64 + bias   vcg_conv2d_nhwc_bf16_fwd_epilogue
+            final/concat + final/1x1 + final/add                                         vcg_incep_join_bf16_fwd on (a1, b2, c3) and m
+        2-path block (model.py:416-439), 4 launches:
+            a/1, b/1 (32, 19 channels) + b/2's BN + PReLU                                vcg_incep_head_bf16_fwd
+            b/2 1xk 19->25 + b/3's BN + PReLU; b/3 kx1 25->32 + bias                     vcg_conv2d_nhwc_bf16_fwd_epilogue
+            final/concat + final/1x1 + final/add                                         vcg_incep_join_bf16_fwd on (a1, b3) and m
+        prefinal/conv2d + batch_norm + Add(long skip)                                    vcg_conv2d_bf16_fwd (kernel = c_block_kernel)
+        upscaling/i/block (64 -> 256 -> 256) and final/conv 9x9 256->3 + tanh            Bf16Generator's tail, kernel = c_block_kernel
+
+    A tensor with one consumer is stored behind that consumer's BatchNormalization + PReLU (pre-activation mini-blocks, model.py:372-382);
+    19-, 25- and 48-channel tensors are stored on 32 / 32 / 64 channels, zeros in the padding (include/vcg.h).  _fold, _pack, the tail with its
+    row bands and uint8 frames, capture / replay / predict / upscale_frames are Bf16Generator's."""
+    SERVED = "bf16 inference of make_upscaler_incep_resnet is instantiated for filters=64 on 3-channel (RGB) frames, upscale_factor a power " \
+             "of two >= 2, block types '3path' (kernel 3 or 5) and '2path' (kernel 3, 5 or 7) in any number, and c_block_kernel 3 or 5; use " \
+             "model.predict for other shapes"
+
+    def __init__(self, model):
+        cfg = getattr(model, "incep_resnet_generator", None)
+        if cfg is None or not hasattr(model, "graph"):
+            raise TypeError("Bf16IncepResnetGenerator serves make_upscaler_incep_resnet models")
+        f = cfg["upscale_factor"]
+        ok = cfg["filters"] == 64 and cfg["channels"] == 3 and isinstance(f, int) and f >= 2 and f & (f - 1) == 0 and cfg["c_block_kernel"] in (3, 5)
+        self.groups = []
+        for tag in ("a", "b", "c"):
+            btype, num, kern = cfg[tag + "_block_type"], cfg[tag + "_block_num"], cfg[tag + "_block_kernel"]
+            if num and (btype not in ("3path", "2path") or kern not in {"3path": (3, 5), "2path": (3, 5, 7)}[btype]):
+                ok = False
+            self.groups.append((tag.upper() if tag != "c" else "c", btype, num, kern))          # 'c' in lower case: model.py:479,481
+        if not ok:
+            raise NotImplementedError(self.SERVED)
+        self.k = cfg["c_block_kernel"]
+        self.legacy = False
+        self.instance = False
+        self.model = model
+        self.rt = model.rt
+        self.layers = {l.name: l for l in model.layers}
+        self._graphs = {}
+        self._bufs = {}
+        self._taps = None
+        self.refresh()
+
+    # ---- parameters ------------------------------------------------------------------------------------------
+    def _block(self, n, btype, k):
+        """the launches of one block: head paths, middle layers, join sources; a tensor is named after the layer whose OUTPUT it is"""
+        rt, ps = self.rt, self.model.ps
+        conv_name = lambda mini, kh, kw: "%s/%s/%dx%d" % (n, mini, kh, kw)
+        if btype == "3path":       # (mini-block, kernel, cout, its single consumer's mini-block or None, input buffer, output buffer)
+            heads = [("a/1", 32, None, "hA"), ("b/1", 32, "b/2", "hB"), ("c/1", 32, "c/2", "hC")]
+            mids = [("b/2", (k, k), 32, 32, None, "hB", "t32"), ("c/2", (k, k), 32, 48, "c/3", "hC", "t64"), ("c/3", (k, k), 48, 64, None, "t64", "u64")]
+            srcs = [("hA", 32), ("t32", 32), ("u64", 64)]
+        else:
+            heads = [("a/1", 32, None, "hA"), ("b/1", 19, "b/2", "hB")]
+            mids = [("b/2", (1, k), 19, 25, "b/3", "hB", "t32"), ("b/3", (k, 1), 25, 32, None, "t32", "hC")]
+            srcs = [("hA", 32), ("hC", 32)]
+
+        def epilogue(conv, nxt):
+            """the layer's bias and, where its output has one consumer, that mini-block's BatchNormalization + PReLU"""
+            if nxt is None:
+                return E.incep_fold(rt, ps, self.layers[conv].cout, bias=conv) + (conv,)
+            return E.incep_fold(rt, ps, self.layers[conv].cout, bias=conv, norm="%s/%s/batch_norm" % (n, nxt), prelu="%s/%s/prelu" % (n, nxt)) \
+                + ("%s/%s/prelu" % (n, nxt),)
+
+        blk = {"name": n, "heads": [], "mids": [], "srcs": []}
+        for mini, cout, nxt, out in heads:
+            conv = conv_name(mini, 1, 1)
+            pre = E.incep_fold(rt, ps, 64, norm="%s/%s/batch_norm" % (n, mini), prelu="%s/%s/prelu" % (n, mini))
+            blk["heads"].append({"cout": cout, "pre": pre, "w": E.pack_incep_frag_bf16(rt, ps[conv + "/kernel"], 1, 64, cout), "ep": epilogue(conv, nxt),
+                                 "out": out})
+        for mini, (kh, kw), cin, cout, nxt, src, out in mids:
+            conv = conv_name(mini, kh, kw)
+            blk["mids"].append({"kh": kh, "kw": kw, "cin": cin, "cout": cout, "w": E.pack_incep_frag_bf16(rt, ps[conv + "/kernel"], kh * kw, cin, cout),
+                                "ep": epilogue(conv, nxt), "in": src, "out": out})
+        total, k0 = sum(c for _, c in srcs), 0
+        for src, c in srcs:
+            blk["srcs"].append((src, c, E.pack_incep_frag_bf16(rt, ps[n + "/final/1x1/kernel"], 1, total, 64, k0, c)))
+            k0 += c
+        blk["bias"] = ps[n + "/final/1x1/bias"]
+        return blk
+
+    def refresh(self):
+        """(re)derive the packed bf16 weights and the folded BatchNormalization vectors from the model's parameters"""
+        rt, ly, ps = self.rt, self.layers, self.model.ps
+        self.first = (E.pack_first9x9_bf16(rt, ps["initial/conv/9x9/kernel"]), ps["initial/conv/9x9/bias"], None)
+        self.blocks = []
+        for tag, btype, num, kern in self.groups:
+            for index in range(num):
+                self.blocks.append(self._block("inc_res_block/%s/%s/%d" % (tag, {"3path": "3p", "2path": "2p"}[btype], index), btype, kern))
+        cp = ly["prefinal/conv2d"]
+        self.prefinal = (self._pack(cp, 1),) + tuple(self._fold(cp, ly["prefinal/batch_norm"]))
+        self.up_layers = []
+        while "upscaling/%d/block/conv_transp" % len(self.up_layers) in ly:
+            self.up_layers.append(ly["upscaling/%d/block/conv_transp" % len(self.up_layers)])
+        self.ups = [(self._pack(up, 0), ps[up.name + "/bias"], float(up.alpha), up.cin) for up in self.up_layers]
+        self.final = (E.pack_final9x9_bf16(rt, ps["final/conv/kernel"]), ps["final/conv/bias"])
+        self._graphs.clear()          # recorded graphs hold the old parameter buffers
+        self._staging = None          # upscale_frames' pinned and device staging buffers
+
+    # ---- one forward pass ------------------------------------------------------------------------------------
+    def _trunk_buffers(self, n, h, w):
+        key = ("trunk", n, h, w)
+        if key not in self._bufs:
+            bf = lambda c: torch.empty(n, h, w, c, dtype=torch.bfloat16, device=self.rt.device)
+            self._bufs[key] = {"skip": bf(64), "a": bf(64), "c": bf(64), "t64": bf(64), "u64": bf(64),
+                               "hA": bf(32), "hB": bf(32), "hC": bf(32), "t32": bf(32)}
+        return self._bufs[key]
+
+    def _tap(self, name, t):
+        if self._taps is not None:
+            self._taps[name] = t.clone()
+
+    def _run_block(self, blk, m, out, B, n, h, w):
+        rt = self.rt
+        paths = (L.IncepHeadPath * len(blk["heads"]))()
+        hd = L.IncepHeadDesc(n, h, w, 64, len(blk["heads"]))
+        for i, hp in enumerate(blk["heads"]):
+            (isc, ish, ial), (osc, osh, oal, _) = hp["pre"], hp["ep"]
+            hd.cout[i] = hp["cout"]
+            paths[i] = L.IncepHeadPath(isc.data_ptr(), ish.data_ptr(), ial.data_ptr(), hp["w"].data_ptr(), osc.data_ptr(), osh.data_ptr(),
+                                       oal.data_ptr() if oal is not None else None, B[hp["out"]].data_ptr())
+        L.check(rt.lib.vcg_incep_head_bf16_fwd(ctypes.byref(hd), m.data_ptr(), paths, rt.stream), "vcg_incep_head_bf16_fwd")
+        for hp in blk["heads"]:
+            self._tap(hp["ep"][3], B[hp["out"]])
+        for md in blk["mids"]:
+            sc, sh, al, name = md["ep"]
+            d = L.ConvDesc(n, md["cin"], h, w, md["cout"], h, w, md["kh"], md["kw"], 1, md["kh"] // 2, md["kw"] // 2)
+            ep = L.EpilogueBf16(sc.data_ptr(), sh.data_ptr(), L.ACT_PRELU if al is not None else L.ACT_NONE, 0.0,
+                                al.data_ptr() if al is not None else None, None)
+            L.check(rt.lib.vcg_conv2d_nhwc_bf16_fwd_epilogue(ctypes.byref(d), B[md["in"]].data_ptr(), md["w"].data_ptr(), B[md["out"]].data_ptr(),
+                                                             ctypes.byref(ep), rt.stream), "vcg_conv2d_nhwc_bf16_fwd_epilogue")
+            self._tap(name, B[md["out"]])
+        ns = len(blk["srcs"])
+        jd = L.IncepJoinDesc(n, h, w, 64, ns)
+        for i, (_, c, _) in enumerate(blk["srcs"]):
+            jd.cin[i] = c
+        z = (ctypes.c_void_p * ns)(*[B[s].data_ptr() for s, _, _ in blk["srcs"]])
+        wf = (ctypes.c_void_p * ns)(*[wj.data_ptr() for _, _, wj in blk["srcs"]])
+        L.check(rt.lib.vcg_incep_join_bf16_fwd(ctypes.byref(jd), z, wf, blk["bias"].data_ptr(), m.data_ptr(), out.data_ptr(), rt.stream),
+                "vcg_incep_join_bf16_fwd")
+        self._tap(blk["name"] + "/final/add", out)
+
+    def _trunk(self, x, B, gate=None):
+        n, _, h, w = x.shape
+        self._stem(x, *self.first, B["skip"])
+        self._tap("initial/conv/9x9", B["skip"])
+        cur = B["skip"]                     # block input; outputs ping-pong between "a" and "c", "skip" is never overwritten
+        for blk in self.blocks:
+            out = B["a"] if cur is not B["a"] else B["c"]
+            self._run_block(blk, cur, out, B, n, h, w)
+            cur = out
+        wp, sp, hp = self.prefinal
+        out = B["a"] if cur is not B["a"] else B["c"]
+        self._conv(cur, wp, out, sp, hp, L.ACT_NONE, None, B["skip"], n, h, w)
+        self._tap("prefinal/tanh", out)
+        return out
+
+    def launches(self):
+        """kernel launches of one pass on whole frames in one chunk: stem + 5 / 4 per block + prefinal + the tail's stages + final/conv"""
+        return 1 + sum(1 + len(b["mids"]) + 1 for b in self.blocks) + 1 + len(self.ups) + 1
+
+    def forward(self, x, out_kind=L.OUT_F32_NCHW, band_rows=None, taps=None):
+        """Bf16Generator.forward; taps: a dict that receives a clone of every tensor the trunk stores, keyed by the name of the layer whose
+        output it is -- a convolution's ("initial/conv/9x9", ".../a/1/1x1", ".../b/2/3x3") where the raw sum is stored, the consumer's PReLU
+        (".../b/2/prelu") where the epilogue activates, ".../final/add", "prefinal/tanh" -- and, on the unbanded fp32 path in one chunk, the
+        up-sampling stages' ("upscaling/i/block/conv_transp") and "final/conv": a debugging hook for eager calls, never used inside a capture"""
+        self._taps = taps
+        try:
+            y = super().forward(x, out_kind, band_rows)
+        finally:
+            self._taps = None
+        if taps is not None:
+            n, _, h, w = x.shape
+            B = self._bufs.get((n, h, w))
+            if B is not None and y is B["y"] and B["us"][0].shape[0] == n:
+                for i, u in enumerate(B["us"]):
+                    taps["upscaling/%d/block/conv_transp" % i] = u.clone()
+            taps["final/conv"] = y.clone()
         return y

@@ -37,6 +37,18 @@ class EpilogueBf16(ctypes.Structure):
                 ("prelu_alpha", c_void_p), ("residual", c_void_p), ("stats", c_void_p), ("stats_mode", c_int32)]
 
 
+class IncepHeadDesc(ctypes.Structure):
+    _fields_ = [(k, c_int32) for k in ("n", "h", "w", "cin", "npaths")] + [("cout", c_int32 * 3)]
+
+
+class IncepHeadPath(ctypes.Structure):
+    _fields_ = [(k, c_void_p) for k in ("in_scale", "in_shift", "in_alpha", "wfrag", "out_scale", "out_shift", "out_alpha", "y")]
+
+
+class IncepJoinDesc(ctypes.Structure):
+    _fields_ = [(k, c_int32) for k in ("n", "h", "w", "cout", "nsrc")] + [("cin", c_int32 * 3)]
+
+
 STATS_NONE, STATS_BATCH, STATS_INSTANCE = 0, 1, 2
 E_UNSUPPORTED = -3            # VCG_E_UNSUPPORTED
 OUT_F32_NCHW, OUT_U8_NHWC = 0, 1          # VCG_OUT_*: what vcg_conv9x9_to3_bf16_fwd_window stores
@@ -187,6 +199,14 @@ SIGNATURES = {
     "vcg_lrelu_bwd_bf16": (c_int, [_P, _P, c_float, _P, c_size_t, _P]),
     "vcg_bf16_to_f32": (c_int, [_P, _P, c_size_t, _P]),
     "vcg_f32_to_bf16": (c_int, [_P, _P, c_size_t, _P]),
+    # bf16 inference of make_upscaler_incep_resnet
+    "vcg_incep_padded_channels": (c_int32, [c_int32]),
+    "vcg_incep_frag_bf16_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "vcg_pack_incep_frag_bf16": (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "vcg_incep_fold": (c_int, [_P, _P, _P, _P, _P, _P, c_int32, c_float, _P, _P, _P, _P]),
+    "vcg_incep_head_bf16_fwd": (c_int, [POINTER(IncepHeadDesc), _P, POINTER(IncepHeadPath), _P]),
+    "vcg_conv2d_nhwc_bf16_fwd_epilogue": (c_int, [_D, _P, _P, _P, _EB, _P]),
+    "vcg_incep_join_bf16_fwd": (c_int, [POINTER(IncepJoinDesc), POINTER(c_void_p), POINTER(c_void_p), _P, _P, _P, _P]),
 }
 
 _lib = None
