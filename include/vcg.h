@@ -693,6 +693,36 @@ typedef struct vcg_incep_join_desc {
 int vcg_incep_join_bf16_fwd(const vcg_incep_join_desc* d, const void* const* z, const void* const* wfrag, const float* bias, const void* m,
                             void* y, hipStream_t stream);
 
+/* ---- bf16 VGG19 perceptual loss: the frozen feature extractor behind VGG_LOSS / VGG_MSE_LOSS / VGG_MAE_LOSS (upscaling/upscaler/model.py:101-157;
+ * keras.applications.VGG19 up to block5_conv4) on bf16 NHWC activations.  block1_conv1 + ReLU runs on vcg_conv3ch_bf16_fwd (lrelu_slope 0), the
+ * other fifteen convolutions + ReLU on vcg_conv2d_nhwc_bf16_fwd (VCG_ACT_LRELU, act_alpha 0), their data gradients on vcg_conv2d_nhwc_bf16_dgrad
+ * (mask_src = the ReLU output that feeds the layer, mask_slope 0) and vcg_conv3ch_bf16_dgrad.  The entries below are the rest: bandwidth
+ * kernels, 8 channels (16 bytes) per lane, deterministic (no atomics), hipGraph-capturable.  Tensors are bf16 NHWC with 16-byte aligned
+ * bases. ---- */
+/* MaxPooling2D((2,2), strides (2,2), 'valid') (model.py:101-157: block{1..4}_pool): x [n][h][w][c] -> y [n][h/2][w/2][c] (floor).  Of equal
+ * values the first in row-major order is stored (it matters for -0 / +0 only).  VCG_E_NULL: x or y NULL; VCG_E_SHAPE: n or c <= 0, h < 2 or
+ * w < 2; VCG_E_UNSUPPORTED: c % 8 != 0, a base that is not 16-byte aligned.  No workspace. */
+int vcg_maxpool2x2_nhwc_bf16_fwd(const void* x, void* y, int32_t n, int32_t h, int32_t w, int32_t c, hipStream_t stream);
+/* The backward of that pooling and of the ReLU of the convolution in front of it in one pass (what Keras derives from model.py:101-157):
+ * y_prepool [n][h][w][c] is the pool's input, a ReLU output; dy [n][h/2][w/2][c] the gradient at the pool's output; dz [n][h][w][c] the
+ * gradient in front of the ReLU: dz = dy at the first maximal element of each window in row-major order (the rule of vcg_maxpool2x2_bwd and
+ * torch) if that element is > 0, and 0 everywhere else, rows / columns beyond 2 * floor(h/2), 2 * floor(w/2) included.  Every element of dz
+ * is written.  Refusals as for the forward (any of the three pointers). */
+int vcg_maxpool2x2_relu_nhwc_bf16_bwd(const void* y_prepool, const void* dy, void* dz, int32_t n, int32_t h, int32_t w, int32_t c,
+                                      hipStream_t stream);
+/* The feature term of the perceptual losses (model.py:101-157: K.mean(K.square(.)) / K.mean(K.abs(.)) of the block5_conv4 features) and its
+ * gradient, one pass over f_true and f_pred (bf16, count elements each):
+ *   loss_out[0] = mean((p - t)^2) (VCG_LOSS_MSE) or mean(|p - t|) (VCG_LOSS_MAE); differences and sums in fp32, the sum in a fixed order:
+ *                 wave shuffles, one partial per wave in ws, one wave adds the partials
+ *   dz_pred     = bf16(grad_scale * g * [p > 0]), g = 2 (p - t) / count or sign(p - t) / count (sign(0) = 0): the gradient in FRONT of
+ *                 block5_conv4's ReLU, whose output f_pred is -- what vcg_conv2d_nhwc_bf16_dgrad of that layer reads
+ * ws: vcg_feature_loss_bf16_ws_bytes(count) bytes (0 for count 0; the query is named as the attention tail's are, its exact-size contract is
+ * checked in tests/test_abi_vgg_contract_gpu.py).  VCG_E_NULL: any pointer NULL; VCG_E_SHAPE: count == 0;
+ * VCG_E_UNSUPPORTED: another kind, f_true / f_pred / dz_pred not 16-byte aligned; VCG_E_WORKSPACE: ws_bytes below the query. */
+size_t vcg_feature_loss_bf16_ws_bytes(size_t count);
+int vcg_feature_loss_bf16(const void* f_true, const void* f_pred, size_t count, int32_t kind, float grad_scale, float* loss_out, void* dz_pred,
+                          void* ws, size_t ws_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

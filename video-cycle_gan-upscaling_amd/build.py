@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libvcg_hip.so")
-SOURCES = ["conv_fwd.hip", "conv_rowchain.hip", "conv_transpose.hip", "conv_wgrad.hip", "norm.hip", "elementwise.hip", "dense.hip", "bf16_layout.hip", "bf16_conv3x3_3ch.hip", "bf16_convt3x3.hip", "bf16_conv9x9_to3.hip", "bf16_norm.hip", "bf16_wgrad.hip", "bf16_wgrad9.hip", "bf16_gconv.hip", "bf16_gwgrad.hip", "bf16_head.hip", "bf16_wgrad3.hip", "bf16_attn.hip", "bf16_incep.hip", "api.hip"]
+SOURCES = ["conv_fwd.hip", "conv_rowchain.hip", "conv_transpose.hip", "conv_wgrad.hip", "norm.hip", "elementwise.hip", "dense.hip", "bf16_layout.hip", "bf16_conv3x3_3ch.hip", "bf16_convt3x3.hip", "bf16_conv9x9_to3.hip", "bf16_norm.hip", "bf16_wgrad.hip", "bf16_wgrad9.hip", "bf16_gconv.hip", "bf16_gwgrad.hip", "bf16_head.hip", "bf16_wgrad3.hip", "bf16_attn.hip", "bf16_incep.hip", "bf16_vgg.hip", "api.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
          "-Wno-unused-value", "-Wno-c++20-extensions"]
 

@@ -1194,6 +1194,89 @@ class FirstConvBf16(Conv2D):
         return dx
 
 
+class FrozenConvReluBf16(Conv2D):
+    """Conv2D(f, 3, 'same') + ReLU of a FROZEN network on bf16 NHWC activations -- fifteen of the sixteen layers of the VGG19 feature
+    extractor behind the perceptual losses (model.py:101-157): forward on vcg_conv2d_nhwc_bf16_fwd with the ReLU in its epilogue
+    (VCG_ACT_LRELU, slope 0), data gradient on vcg_conv2d_nhwc_bf16_dgrad, which also applies the ReLU derivative of the layer that FEEDS this
+    one (mask = this layer's input).  No weight gradient exists, so none is asked for: backward is the data gradient only.  The fragments
+    are packed when the weights are set (refresh), never inside a step: a recorded train step holds no pack launch of a frozen layer.
+    Conv2D's parameter names and layouts: the model exchanges weights with the fp32 one."""
+
+    def __init__(self, name, cin, cout):
+        if cin % 32 or cout % 32:
+            raise NotImplementedError("FrozenConvReluBf16 serves 3x3 stride-1 'same' layers on channel counts that are multiples of 32")
+        super().__init__(name, cin, cout, 3, act=L.ACT_LRELU, alpha=0.0)
+        self._pk = PackedOperand(lambda out: pack_conv_frag_bf16_pair(self.rt, self.ps[self.name + "/kernel"], 9, cin, cout, out), self)
+
+    def refresh(self):
+        super().refresh()
+        if self.rt is not None:
+            self._pk.get()
+
+    def forward(self, x, tag=None):
+        """x bf16 NHWC -> relu(conv(x) + bias) bf16 NHWC"""
+        rt = self.rt
+        n, h, w, _ = x.shape
+        d = self.desc(n, h, w)
+        wf, _ = self._pk.get()
+        y = _bf16(rt, n, h, w, self.cout)
+        with Timed(rt, tag):
+            L.check(rt.lib.vcg_conv2d_nhwc_bf16_fwd(ctypes.byref(d), x.data_ptr(), wf.data_ptr(), self.ps[self.name + "/bias"].data_ptr(), L.ACT_LRELU, 0.0,
+                                                    y.data_ptr(), rt.stream), "vcg_conv2d_nhwc_bf16_fwd[%s]" % self.name)
+        return y
+
+    def backward_data(self, dz, relu_input=None, tag=None):
+        """dz: bf16 NHWC gradient in front of this layer's ReLU.  relu_input: the layer's input where that is the ReLU output of another
+        convolution -- the result is then the gradient in front of THAT ReLU; None where the input is a pooled tensor."""
+        rt = self.rt
+        n, h, w, _ = dz.shape
+        d = self.desc(n, h, w)
+        _, wd = self._pk.get()
+        dx = _bf16(rt, n, h, w, self.cin)
+        with Timed(rt, tag and tag + "_dgrad"):
+            L.check(rt.lib.vcg_conv2d_nhwc_bf16_dgrad(ctypes.byref(d), dz.data_ptr(), wd.data_ptr(), _ptr(relu_input), 0.0, dx.data_ptr(), rt.stream),
+                    "vcg_conv2d_nhwc_bf16_dgrad[%s]" % self.name)
+        return dx
+
+
+class FrozenFirstConvReluBf16(Conv2D):
+    """block1_conv1 of that extractor: Conv2D(64, 3, 'same') + ReLU from the fp32 NCHW frames to bf16 NHWC on vcg_conv3ch_bf16_fwd
+    (lrelu_slope 0), data gradient from the bf16 NHWC gradient in front of the ReLU to the fp32 NCHW frames on vcg_conv3ch_bf16_dgrad.
+    Frozen like FrozenConvReluBf16: packed at refresh, no weight gradient."""
+
+    def __init__(self, name, cin, cout):
+        if cin != 3 or cout != 64:
+            raise NotImplementedError("FrozenFirstConvReluBf16 serves Conv2D(64, 3) on 3 input channels")
+        super().__init__(name, cin, cout, 3, act=L.ACT_LRELU, alpha=0.0)
+        self._pk = PackedOperand(lambda out: pack_conv3ch_bf16(self.rt, self.ps[self.name + "/kernel"], 3, 3, cout, out), self)
+
+    def refresh(self):
+        super().refresh()
+        if self.rt is not None:
+            self._pk.get()
+
+    def forward(self, x, tag=None):
+        rt = self.rt
+        n, _, h, w = x.shape
+        d = self.desc(n, h, w)
+        y = _bf16(rt, n, h, w, self.cout)
+        with Timed(rt, tag):
+            L.check(rt.lib.vcg_conv3ch_bf16_fwd(ctypes.byref(d), x.data_ptr(), self._pk.get().data_ptr(), self.ps[self.name + "/bias"].data_ptr(), 0.0,
+                                                y.data_ptr(), rt.stream), "vcg_conv3ch_bf16_fwd[%s]" % self.name)
+        return y
+
+    def backward_data(self, dz, tag=None):
+        rt = self.rt
+        n, h, w, _ = dz.shape
+        d = self.desc(n, h, w)
+        dx = rt.empty(n, self.cin, h, w)
+        ws, wsn = rt.workspace(rt.lib.vcg_conv3ch_bf16_dgrad_workspace_bytes(ctypes.byref(d)))
+        with Timed(rt, tag and tag + "_dgrad"):
+            L.check(rt.lib.vcg_conv3ch_bf16_dgrad(ctypes.byref(d), dz.data_ptr(), self.ps[self.name + "/kernel"].data_ptr(), dx.data_ptr(), ws, wsn,
+                                                  rt.stream), "vcg_conv3ch_bf16_dgrad[%s]" % self.name)
+        return dx
+
+
 class ConvCout1Bf16(Conv2D):
     """Conv2D(1, k) on bf16 NHWC activations -- the 70x70 PatchGAN's last layer (512 -> 1, 4x4, zero padding 1) in the bf16 configs:
     forward, data gradient and weight gradient on vcg_conv2d_cout1_nhwc_bf16_* straight from / to the bf16 NHWC tensor (fp32
@@ -1671,6 +1754,35 @@ def maxpool2x2_bwd(rt, x, dy):
     dx = rt.empty(n, c, h, w)
     L.check(rt.lib.vcg_maxpool2x2_bwd(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), n, c, h, w, rt.stream), "vcg_maxpool2x2_bwd")
     return dx
+
+
+def maxpool2x2_nhwc_bf16(rt, x):
+    """MaxPooling2D((2,2)) forward on bf16 NHWC -> [n,h//2,w//2,c]"""
+    n, h, w, c = x.shape
+    y = _bf16(rt, n, h // 2, w // 2, c)
+    L.check(rt.lib.vcg_maxpool2x2_nhwc_bf16_fwd(x.data_ptr(), y.data_ptr(), n, h, w, c, rt.stream), "vcg_maxpool2x2_nhwc_bf16_fwd")
+    return y
+
+
+def maxpool2x2_relu_nhwc_bf16_bwd(rt, y_prepool, dy):
+    """gradient in front of the ReLU whose output y_prepool the pooling read, from the gradient dy at the pooling's output (bf16 NHWC)"""
+    n, h, w, c = y_prepool.shape
+    dz = torch.empty_like(y_prepool)
+    L.check(rt.lib.vcg_maxpool2x2_relu_nhwc_bf16_bwd(y_prepool.data_ptr(), dy.data_ptr(), dz.data_ptr(), n, h, w, c, rt.stream),
+            "vcg_maxpool2x2_relu_nhwc_bf16_bwd")
+    return dz
+
+
+def feature_loss_bf16(rt, f_true, f_pred, kind, grad_scale, out=None):
+    """(mean squared / absolute difference [1] fp32, bf16 gradient of grad_scale x it in front of the ReLU that produced f_pred) of two bf16
+    feature tensors (vcg_feature_loss_bf16); ``out``: a 1-element fp32 view to write the value to"""
+    if f_true.shape != f_pred.shape or f_true.dtype != torch.bfloat16 or f_pred.dtype != torch.bfloat16:
+        raise TypeError("feature_loss_bf16 takes two bf16 tensors of one shape")
+    val, dz = (rt.empty(1) if out is None else out), torch.empty_like(f_pred)
+    ws, wsn = rt.workspace(rt.lib.vcg_feature_loss_bf16_ws_bytes(f_pred.numel()))
+    L.check(rt.lib.vcg_feature_loss_bf16(f_true.data_ptr(), f_pred.data_ptr(), f_pred.numel(), L.LOSS_MSE if kind == "mse" else L.LOSS_MAE,
+                                         float(grad_scale), val.data_ptr(), dz.data_ptr(), ws, wsn, rt.stream), "vcg_feature_loss_bf16")
+    return val, dz
 
 
 def mean_scalar(rt, t, out=None):

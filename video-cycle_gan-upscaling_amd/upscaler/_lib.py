@@ -207,6 +207,11 @@ SIGNATURES = {
     "vcg_incep_head_bf16_fwd": (c_int, [POINTER(IncepHeadDesc), _P, POINTER(IncepHeadPath), _P]),
     "vcg_conv2d_nhwc_bf16_fwd_epilogue": (c_int, [_D, _P, _P, _P, _EB, _P]),
     "vcg_incep_join_bf16_fwd": (c_int, [POINTER(IncepJoinDesc), POINTER(c_void_p), POINTER(c_void_p), _P, _P, _P, _P]),
+    # bf16 VGG19 perceptual loss
+    "vcg_maxpool2x2_nhwc_bf16_fwd": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
+    "vcg_maxpool2x2_relu_nhwc_bf16_bwd": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
+    "vcg_feature_loss_bf16_ws_bytes": (c_size_t, [c_size_t]),
+    "vcg_feature_loss_bf16": (c_int, [_P, _P, c_size_t, c_int32, c_float, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

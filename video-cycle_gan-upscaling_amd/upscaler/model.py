@@ -83,15 +83,26 @@ class _VggLossBase:
     make.  ``vgg19`` therefore names the weights instead of being a Keras model: a ``VGG19Features`` instance, a
     path to a .safetensors / .npz archive or a dict with Keras' layer names (``block1_conv1/kernel`` (3,3,3,64) ...
     ``block5_conv4/bias``), or the string ``'random'`` (seeded He-uniform: throughput runs and parity tests).
-    ``vgg19=None`` raises, because silently training against random features is not what the caller asked for."""
+    ``vgg19=None`` raises, because silently training against random features is not what the caller asked for.
+
+    ``dtype='bf16'`` builds the extractor on bf16 activations (VGG19Features(dtype='bf16')); a ``VGG19Features`` instance keeps its own dtype,
+    and a ``dtype`` that contradicts it raises ValueError."""
     kind, rate = "vgg", 0.0
 
-    def __init__(self, image_shape, vgg19=None):
+    def __init__(self, image_shape, vgg19=None, dtype=None):
         self.image_shape = tuple(image_shape)
+        if dtype not in (None, "fp32", "bf16"):
+            raise ValueError("dtype must be 'fp32' or 'bf16', got %r" % (dtype,))
         if vgg19 is None:
             raise RuntimeError("VGG19 ImageNet weights cannot be downloaded here: pass vgg19=<path to a .safetensors/.npz with "
                                "Keras' VGG19 layer names> (or a dict of arrays), or vgg19='random' for synthetic runs")
-        self.model = vgg19 if isinstance(vgg19, VGG19Features) else VGG19Features(self.image_shape, vgg19)
+        if isinstance(vgg19, VGG19Features):
+            if dtype is not None and dtype != vgg19.dtype:
+                raise ValueError("dtype=%r contradicts the %s VGG19Features instance passed as vgg19=" % (dtype, vgg19.dtype))
+            self.model = vgg19
+        else:
+            self.model = VGG19Features(self.image_shape, vgg19, dtype=dtype or "fp32")
+        self.dtype = self.model.dtype
         self.model.trainable = False
 
     def loss(self, y_true, y_pred):
@@ -111,8 +122,8 @@ class VGG_MSE_LOSS(_VggLossBase):
     """VGG_LOSS + mse_loss_rate * pixel MSE (model.py:119-137)"""
     kind = "vgg_mse"
 
-    def __init__(self, image_shape, mse_loss_rate=0.1, vgg19=None):
-        super().__init__(image_shape, vgg19)
+    def __init__(self, image_shape, mse_loss_rate=0.1, vgg19=None, dtype=None):
+        super().__init__(image_shape, vgg19, dtype)
         self.mse_loss_rate = self.rate = float(mse_loss_rate)
 
 
@@ -120,8 +131,8 @@ class VGG_MAE_LOSS(_VggLossBase):
     """mean|VGG(y_true) - VGG(y_pred)| + mae_loss_rate * pixel MAE (model.py:139-157)"""
     kind = "vgg_mae"
 
-    def __init__(self, image_shape, mae_loss_rate=0.1, vgg19=None):
-        super().__init__(image_shape, vgg19)
+    def __init__(self, image_shape, mae_loss_rate=0.1, vgg19=None, dtype=None):
+        super().__init__(image_shape, vgg19, dtype)
         self.mae_loss_rate = self.rate = float(mae_loss_rate)
 
 
@@ -338,17 +349,35 @@ class Model:
 class VGG19Features(Model):
     """keras.applications.VGG19(include_top=False) up to block5_conv4 -- the frozen feature extractor of the perceptual
     losses (model.py:108-112).  3x3 'same' convolutions with fused ReLU, 2x2 max pooling after blocks 1-4; only the
-    data gradient is ever needed (``backward_data``)."""
+    data gradient is ever needed (``backward_data``).
 
-    def __init__(self, image_shape, weights="random", seed=19):
+    ``dtype='bf16'``: the same sixteen layers under the same names and parameter layouts (the weights dict is that of the fp32 model) on bf16
+    NHWC activations -- E.FrozenFirstConvReluBf16 / E.FrozenConvReluBf16, vcg_maxpool2x2_nhwc_bf16_fwd, and in the backward
+    vcg_maxpool2x2_relu_nhwc_bf16_bwd.  ``forward`` then takes the fp32 NCHW frames and returns the bf16 NHWC block5_conv4 features with the
+    list of the sixteen stored ReLU outputs as its tape; ``backward_data`` takes the bf16 NHWC gradient IN FRONT of block5_conv4's ReLU
+    (what vcg_feature_loss_bf16 writes) and returns the fp32 NCHW image gradient.  Shapes the kernels do not serve raise
+    NotImplementedError(VGG_BF16_SERVED): there is no fp32 fallback."""
+
+    VGG_BF16_SERVED = "VGG19Features(dtype='bf16') serves frames of 3 channels with height and width of at least 16"
+
+    def __init__(self, image_shape, weights="random", seed=19, dtype="fp32"):
+        if dtype not in ("fp32", "bf16"):
+            raise ValueError("dtype must be 'fp32' or 'bf16', got %r" % (dtype,))
+        if dtype == "bf16" and (len(image_shape) != 3 or image_shape[2] != 3 or min(image_shape[0], image_shape[1]) < 16):
+            raise NotImplementedError(self.VGG_BF16_SERVED)
         super().__init__("vgg19_block5_conv4", image_shape, seed)
         self.trainable = False
+        self.dtype = dtype
         self.stages = []
         cin = image_shape[2]
         for b, nconv, f in VGG19_BLOCKS:
             convs = []
             for i in range(nconv):
-                convs.append(self._add(E.Conv2D("block%d_conv%d" % (b, i + 1), cin, f, 3, act=L.ACT_LRELU, alpha=0.0)))
+                name = "block%d_conv%d" % (b, i + 1)
+                if dtype == "bf16":
+                    convs.append(self._add(E.FrozenFirstConvReluBf16(name, cin, f) if cin == 3 else E.FrozenConvReluBf16(name, cin, f)))
+                else:
+                    convs.append(self._add(E.Conv2D(name, cin, f, 3, act=L.ACT_LRELU, alpha=0.0)))
                 cin = f
             self.stages.append((convs, b < 5))
         self._finish()
@@ -374,20 +403,62 @@ class VGG19Features(Model):
     def _out_shape(self, s):
         return (s[0] // 16, s[1] // 16, 512)
 
-    def forward(self, x, training=False):
+    def forward(self, x, training=False, taps=None):
+        if self.dtype == "bf16":
+            return self._forward_bf16(x, training, taps)
         tape = []
         h = x
         for convs, pool in self.stages:
             for c in convs:
                 h, a = c.forward(h, tag="vgg_conv")
                 tape.append(a)
+                if taps is not None:
+                    taps.append(h)
             if pool:
                 tape.append(h)
                 h = E.maxpool2x2(self.rt, h)
         return h, tape
 
+    def _forward_bf16(self, x, training, taps):
+        """fp32 NCHW frames -> (bf16 NHWC block5_conv4 features, tape).  The tape is the list of the sixteen stored ReLU outputs -- all the
+        backward needs: the masks, the pooling inputs and the shapes -- and is kept only in training mode (the real frames need none)."""
+        if x.dim() != 4 or x.dtype != torch.float32 or x.shape[1] != 3 or min(x.shape[2], x.shape[3]) < 16:
+            raise NotImplementedError(self.VGG_BF16_SERVED + " (fp32 NCHW); got %s %s" % (x.dtype, tuple(x.shape)))
+        tape = [] if training else None
+        h = x
+        for convs, pool in self.stages:
+            for c in convs:
+                h = c.forward(h, tag="vgg_conv")
+                if tape is not None:
+                    tape.append(h)
+                if taps is not None:
+                    taps.append(h)
+            if pool:
+                h = E.maxpool2x2_nhwc_bf16(self.rt, h)
+        return h, tape
+
+    def _backward_data_bf16(self, tape, dz):
+        if tape is None or len(tape) != 16:
+            raise RuntimeError("backward_data needs the tape of a training-mode forward (the sixteen stored ReLU outputs)")
+        if dz.dtype != torch.bfloat16 or tuple(dz.shape) != tuple(tape[-1].shape):
+            raise TypeError("backward_data(dtype='bf16') takes the bf16 NHWC gradient in front of block5_conv4's ReLU, shape %s" % (tuple(tape[-1].shape),))
+        layers = [(c, i == 0) for convs, _ in self.stages for i, c in enumerate(convs)]
+        d = dz
+        for k in range(15, 0, -1):
+            c, first_in_block = layers[k]
+            if first_in_block:      # the input is a pooled tensor: the plain data gradient, then pooling + ReLU backward in one pass
+                d = E.maxpool2x2_relu_nhwc_bf16_bwd(self.rt, tape[k - 1], c.backward_data(d, None, tag="vgg_conv"))
+            else:                   # the input is the ReLU output of layer k - 1: its derivative rides in the data gradient's epilogue
+                d = c.backward_data(d, tape[k - 1], tag="vgg_conv")
+        return layers[0][0].backward_data(d, tag="vgg_conv")
+
+    def _export(self, y):
+        return E.bf16_to_f32(self.rt, y) if y.dtype == torch.bfloat16 else super()._export(y)
+
     def backward_data(self, tape, dy):
         """dL/d(input image) from dL/d(features); no parameter gradients (the network is frozen)"""
+        if self.dtype == "bf16":
+            return self._backward_data_bf16(tape, dy)
         tape = list(tape)
         d = dy
         for convs, pool in reversed(self.stages):
@@ -808,9 +879,20 @@ def _content_loss_and_grad(rt, kind, weight, fake, hr, out=None):
     if isinstance(kind, str):
         return _pixel_loss(rt, fake, hr, kind, weight, out)
     vgg = kind.model
+    pk = "mae" if kind.kind == "vgg_mae" else "mse"
+    if vgg.dtype == "bf16":
+        # features on bf16 activations; the loss kernel leaves the gradient in front of block5_conv4's ReLU, backward_data returns fp32 NCHW
+        f_real, _ = vgg.forward(hr)
+        f_fake, tape = vgg.forward(fake, training=True)
+        val, dz = E.feature_loss_bf16(rt, f_real, f_fake, pk, weight, out)
+        dfake = vgg.backward_data(tape, dz)
+        if kind.rate:
+            pval, dpix = _pixel_loss(rt, fake, hr, pk, weight * kind.rate)
+            E.axpby(rt, dpix, dfake, 1.0, 1.0)
+            E.axpby(rt, pval, val, kind.rate, 1.0)
+        return val, dfake
     f_real, _ = vgg.forward(hr)
     f_fake, tape = vgg.forward(fake)
-    pk = "mae" if kind.kind == "vgg_mae" else "mse"
     val, dfeat = _pixel_loss(rt, f_fake, f_real, pk, weight, out)
     dfake = vgg.backward_data(tape, dfeat)
     if kind.rate:
